@@ -21,8 +21,11 @@ replays a hipGraph: System-2 ViT + prefill of the 6- or 7-env micro-batch; then 
 concurrently with System-1 of the 57-58 other envs on a side stream; then System-1 of the micro-batch's envs (same results as the
 single-stream order, checked before the timed region). Noise draw, micro-batch gather/scatter, D2H of the trajectories and the host
 post-processing (traj_to_actions; for the side-stream envs it runs while the GPU finishes the main stream) are inside the step.
-After the timed region rank 0 runs ONE instrumented eager pass with per-launch HIP events (ina_prof_*) to attribute time and
-algorithmic FLOPs to kernel classes for the "roofline" object, and (N = 1 only) times the CPU oracle on a bounded sample.
+A plain run stops there and prints the line ("roofline" and "cpu_baseline" null). With --full, the two-stream schedule is first
+checked against the single-stream order, and after the timed region rank 0 runs a calibration GEMM, ONE instrumented eager pass
+with per-launch HIP events (ina_prof_*) to attribute time and algorithmic FLOPs to kernel classes for the "roofline" object, the
+schedule variants (n1_dual) and (N = 1 only) times the CPU oracle on a bounded sample. --dump-outputs DIR writes what the last
+timed step returned as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -91,6 +94,11 @@ def parse():
                     help="n1_dual: the round-4 launches for the row-local part of the NextDiT blocks (GEMM, norm, GEMM) instead of the row-chain kernel")
     # (round-3 schedule experiments - stream priorities, System-1 started with the prefill, early look-down encoding, a split side-stream
     #  call - were all measured neutral or negative, profiles/r03d/e/f/u_*; their switches are gone)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything besides the headline: the two-stream schedule check, the calibration "
+                         "GEMM, the instrumented roofline pass, the variants (n1_dual) and the CPU baseline. A plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (actions, trajectories, System-2 tokens / latents, ...) as DIR/<name>.npy, float32")
     a, rest = ap.parse_known_args()
     if rest and a.workload != "sft":
         ap.error(f"unrecognized arguments: {' '.join(rest)}")
@@ -104,7 +112,7 @@ def default_args(**kw):
     """the parsed defaults as a namespace (tools/ construct workloads without a command line)"""
     a = argparse.Namespace(gpus=1, steps=20, warmup=3, envs=64, workload="n1_dual", cadence="nominal", num_history=3, lookdown=False, no_cpu_baseline=True, dit_ffn=1536,
                            no_graph=False, no_overlap=False, vit_cache=False, prefix_kv=False, no_split_prefill=False, s2_every=1, no_row_chain=False,
-                           no_frag_weights=False, no_fuse_decode_rope=False, no_variants=True, rest=[])
+                           no_frag_weights=False, no_fuse_decode_rope=False, no_variants=True, full=False, dump_outputs=None, rest=[])
     for k, v in kw.items():
         assert hasattr(a, k), k
         setattr(a, k, v)
@@ -169,7 +177,7 @@ class NavDPS1:
         self.inp["x_init"].normal_(generator=self.g)
         self.inp["step_noise"].normal_(generator=self.g)
         neg, pos = self.graph() if self.graph else self._call(**self.inp)
-        self.last_out = pos
+        self.last_out, self.last_neg = pos, neg
         return pos
 
     def instrumented(self):
@@ -178,11 +186,15 @@ class NavDPS1:
     def step_output_for_check(self):
         return self.last_out
 
+    def outputs(self):
+        """the two action sets predict_pointgoal_batch_action_vel returned in the last step"""
+        return {"pos": self.last_out, "neg": self.last_neg}
+
     def cpu_baseline(self):
         from internnav_amd import synthetic
         from oracle import navdp as o_navdp  # cpu_baseline leg only
 
-        cores = min(64, os.cpu_count() or 1)
+        cores = cpu_cores()
         torch.set_num_threads(cores)
         sd = synthetic.navdpnet_state_dict(0)
         inp = synthetic.navdpnet_inputs(1, 0)
@@ -235,11 +247,14 @@ class UNet1DS1:
     def step_output_for_check(self):
         return self.last_out
 
+    def outputs(self):
+        return {"traj": self.last_out}
+
     def cpu_baseline(self):
         from internnav_amd import synthetic
         from oracle import unet1d as o_u  # cpu_baseline leg only
 
-        cores = min(64, os.cpu_count() or 1)
+        cores = cpu_cores()
         torch.set_num_threads(cores)
         sd = synthetic.materialize(synthetic.unet1d_spec(self.cfg), 0)
         inp = synthetic.unet1d_inputs(1, 0, self.cfg)
@@ -286,6 +301,9 @@ class HostStub:
 
     def step_output_for_check(self):
         return self.actions
+
+    def outputs(self):
+        return {"actions": self.actions}
 
 
 class N1Dual:
@@ -701,6 +719,7 @@ class N1Dual:
         return self.actions
 
     def step(self, i):
+        self.last_i = i
         if self.overlap:
             return self.step_overlapped(i)
         j = i % self.PERIOD
@@ -745,6 +764,26 @@ class N1Dual:
     def step_output_for_check(self):
         return self.actions
 
+    def outputs(self):
+        """what the last step handed its caller: the action table, the System-1 trajectories of every env (zeros for an env without a
+        System-1 call in that step; two-stream schedule: the host copies the post-processing read) and the greedy tokens + latent queries
+        of the step's System-2 micro-batch"""
+        j = self.last_i % self.PERIOD
+        m, lo = self.mb[j], int(self.mb_start[j])
+        out = {"actions": self.actions}
+        if self.with_s1:
+            if self.overlap and m > 0:
+                hostidx = self.idxA_host[j]
+                traj = torch.zeros(self.B, *self.hostA.shape[1:])
+                traj[hostidx] = self.hostA[:len(hostidx)]
+                traj[lo:lo + m] = self.hostB[:m]
+            else:
+                traj = self.last_traj
+            out["traj"] = traj
+        if m > 0:
+            out["s2_tokens"], out["s2_latents"] = self.s2[m]["toks"], self.s2[m]["lat"]
+        return out
+
     def instrumented(self):
         m = max(self.mb)
         q = self.model.qwen
@@ -780,7 +819,7 @@ def n1_cpu_baseline(qc, grids, pv_rows, ids, n_decode, cadence, with_s1, unit, d
     from oracle import nextdit as o_nd  # cpu_baseline leg only
     from oracle import qwen_vl as o_q
 
-    cores = min(64, os.cpu_count() or 1)
+    cores = cpu_cores()
     torch.set_num_threads(cores)
     out = {}
     t_s1 = 0.0
@@ -884,7 +923,7 @@ def n1_variants(a, steps: int = 10, warmup: int = 3) -> dict:
     out = {}
     for name, flags in (("prefix_kv", ["--prefix-kv"]), ("s2_every2", ["--s2-every", "2"]), ("dit_ffn_1024", ["--dit-ffn", "1024"])):
         cmd = [sys.executable, str(Path(__file__).resolve()), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--envs", str(a.envs),
-               "--no-cpu-baseline", "--no-variants"] + flags
+               "--full", "--no-cpu-baseline", "--no-variants"] + flags
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
@@ -909,6 +948,16 @@ def _median_time(fn, runs: int, autocast: bool = False) -> float:
     return sorted(ts)[len(ts) // 2]
 
 
+def cpu_cores() -> int:
+    """host threads of a CPU leg: at most 64, no more than the cores this process may run on, and no more than OMP_NUM_THREADS when the
+    job sets it (os.cpu_count() is the whole machine's, and an oversubscribed thread pool only slows itself down)"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, min(64, n))
+
+
 def _cpu_model() -> str:
     try:
         for line in open("/proc/cpuinfo"):
@@ -917,6 +966,29 @@ def _cpu_model() -> str:
     except OSError:
         pass
     return "unknown"
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(dirname, arrays: dict) -> dict:
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (float64 stays float64), so that two builds run with the same arguments
+    can be compared output for output. An array above a quarter of the 64 MB budget is replaced by a fixed, seeded sample of its
+    flattened elements (same indices on every run). Returns {name: stored shape}."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    total, shapes = 0, {}
+    for name, x in arrays.items():
+        x = x.detach().float().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        x = x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+        if x.nbytes > DUMP_LIMIT_BYTES // 4:
+            k = DUMP_LIMIT_BYTES // 4 // x.itemsize
+            x = x.reshape(-1)[np.sort(np.random.default_rng(0).choice(x.size, k, replace=False))]
+        total += x.nbytes
+        assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: more than {DUMP_LIMIT_BYTES >> 20} MB"
+        np.save(d / f"{name}.npy", x)
+        shapes[name] = list(x.shape)
+    return shapes
 
 
 def pmc_traffic(workload, kernel=None):
@@ -936,6 +1008,46 @@ def pmc_traffic(workload, kernel=None):
     return {"bytes_per_launch": round((t["read_MB_per_launch_x2_corrected"] + t["write_MB_per_launch"]) * 1e6), "kernel": t["kernel"], "source": t["source"]}
 
 
+def instrumented_roofline(a, wl, value, world) -> dict:
+    """roofline: one instrumented eager pass, HIP events around every launch on the launch stream"""
+    from internnav_amd import runtime
+
+    runtime.prof_enable(True)
+    extra = wl.instrumented()
+    torch.cuda.synchronize()
+    prof = runtime.prof_read()
+    per_kernel = runtime.prof_read_gemm_kernels()
+    runtime.prof_enable(False)               # (also clears the tally)
+    gm = prof["gemm"]
+    blend = gm["flops"] / (gm["ms"] * 1e-3) / 1e12 if gm["ms"] > 0 else 0.0
+    # the dominant kernel = the named kernel with the largest share of the step's GEMM time
+    dom_name, dom = max(per_kernel.items(), key=lambda kv: kv[1]["ms"]) if per_kernel else ("none", dict(ms=0.0, launches=0, flops=0.0))
+    achieved = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
+    step_tflops = (value / world) * wl.f_alg / 1e12
+    return {
+        "bound": "mfma", "kernel": dom_name,
+        "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+        # the same fraction over ALL tiled MFMA GEMM launches of the pass: a launch moving to another tile kernel cannot change it
+        "frac_gemm_class_blend": round(blend / PEAK_BF16_TFLOPS, 4),
+        "launches": dom["launches"], "avg_launch_us": round(dom["ms"] * 1e3 / max(dom["launches"], 1), 2),
+        "algorithmic_tflop_per_launch": round(dom["flops"] / max(dom["launches"], 1) / 1e12, 4),
+        "algorithmic_mbytes_per_launch": round(dom.get("bytes", 0.0) / max(dom["launches"], 1) / 1e6, 1),      # operands + output once (2MK + 2NK + out)
+        "traffic": pmc_traffic(a.workload, dom_name),
+        "gemm_class_blend": {"what": "all tiled MFMA GEMM launches of the instrumented pass (every tile config)", "achieved": round(blend, 1),
+                             "frac": round(blend / PEAK_BF16_TFLOPS, 4)},
+        "per_kernel": {k: {"launches": v["launches"], "ms": round(v["ms"], 3), "tflop": round(v["flops"] / 1e12, 3), "gbyte": round(v.get("bytes", 0.0) / 1e9, 2),
+                           "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1)} for k, v in per_kernel.items()},
+        "instrumented_pass": {"what": extra if isinstance(extra, str) else "one engine call over all envs",
+                              "gemm_launches": gm["launches"], "gemm_avg_launch_us": round(gm["ms"] * 1e3 / max(gm["launches"], 1), 2),
+                              "gemm_tflop": round(gm["flops"] / 1e12, 3),
+                              "kernel_class_ms": {k: round(v["ms"], 3) for k, v in prof.items()},
+                              "kernel_class_tflops": {k: round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1) for k, v in prof.items()},
+                              "kernel_class_algorithmic_GBps": {k: round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1) for k, v in prof.items()}},
+        "whole_step": {"algorithmic_tflop_per_env_step": round(wl.f_alg / 1e12, 4),
+                       "achieved_tflops_per_gpu": round(step_tflops, 1), "frac": round(step_tflops / PEAK_BF16_TFLOPS, 4)},
+    }
+
+
 # ------------------------------------------------------------------------------------------------------------ driver
 def main():
     a = parse()
@@ -946,7 +1058,8 @@ def main():
         import bench_sft
 
         sys.argv = [str(ROOT / "bench_sft.py"), "--gpus", str(a.gpus), "--steps", str(a.steps), "--warmup", str(a.warmup)] + \
-                   (["--no-cpu-baseline"] if a.no_cpu_baseline else []) + a.rest
+                   (["--no-cpu-baseline"] if a.no_cpu_baseline else []) + (["--full"] if a.full else []) + \
+                   (["--dump-outputs", a.dump_outputs] if a.dump_outputs else []) + a.rest
         return bench_sft.main()
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1011,7 +1124,7 @@ def main():
                 torch.cuda.synchronize()
 
     overlap_check = None
-    if getattr(wl, "overlap", False):
+    if a.full and getattr(wl, "overlap", False):
         overlap_check = wl.check_overlap()
     for i in range(a.warmup):
         step(i)
@@ -1039,6 +1152,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     value = world * wl.B * a.steps / dt
+    if rank == 0 and a.dump_outputs:
+        # before anything else runs on the engine buffers the last step left behind (rank 0's envs; N > 1: + everybody's actions)
+        write_outputs(a.dump_outputs, dict(wl.outputs(), **({"actions_all_ranks": gathered} if world > 1 else {})))
 
     if rank == 0 and host_stub:
         # rank 0 alone in the post-run section (the GPU workloads run their instrumented pass and the CPU baseline here) while the others wait
@@ -1051,42 +1167,9 @@ def main():
                                           "host_cores_per_rank": pinned, "host_cores": len(os.sched_getaffinity(0)) if pinned is None else None}, **wl.desc),
                           "roofline": None, "cpu_baseline": None}), flush=True)
     elif rank == 0:
-        calib = calibration_gemm(dev)
-        # ---- roofline: one instrumented eager pass, HIP events around every launch on the launch stream
-        runtime.prof_enable(True)
-        extra = wl.instrumented()
-        torch.cuda.synchronize()
-        prof = runtime.prof_read()
-        per_kernel = runtime.prof_read_gemm_kernels()
-        runtime.prof_enable(False)               # (also clears the tally)
-        gm = prof["gemm"]
-        blend = gm["flops"] / (gm["ms"] * 1e-3) / 1e12 if gm["ms"] > 0 else 0.0
-        # the dominant kernel = the named kernel with the largest share of the step's GEMM time
-        dom_name, dom = max(per_kernel.items(), key=lambda kv: kv[1]["ms"]) if per_kernel else ("none", dict(ms=0.0, launches=0, flops=0.0))
-        achieved = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
-        step_tflops = (value / world) * wl.f_alg / 1e12
-        roofline = {
-            "bound": "mfma", "kernel": dom_name,
-            "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-            # the same fraction over ALL tiled MFMA GEMM launches of the pass: a launch moving to another tile kernel cannot change it
-            "frac_gemm_class_blend": round(blend / PEAK_BF16_TFLOPS, 4),
-            "launches": dom["launches"], "avg_launch_us": round(dom["ms"] * 1e3 / max(dom["launches"], 1), 2),
-            "algorithmic_tflop_per_launch": round(dom["flops"] / max(dom["launches"], 1) / 1e12, 4),
-            "algorithmic_mbytes_per_launch": round(dom.get("bytes", 0.0) / max(dom["launches"], 1) / 1e6, 1),      # operands + output once (2MK + 2NK + out)
-            "traffic": pmc_traffic(a.workload, dom_name),
-            "gemm_class_blend": {"what": "all tiled MFMA GEMM launches of the instrumented pass (every tile config)", "achieved": round(blend, 1),
-                                 "frac": round(blend / PEAK_BF16_TFLOPS, 4)},
-            "per_kernel": {k: {"launches": v["launches"], "ms": round(v["ms"], 3), "tflop": round(v["flops"] / 1e12, 3), "gbyte": round(v.get("bytes", 0.0) / 1e9, 2),
-                               "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1)} for k, v in per_kernel.items()},
-            "instrumented_pass": {"what": extra if isinstance(extra, str) else "one engine call over all envs",
-                                  "gemm_launches": gm["launches"], "gemm_avg_launch_us": round(gm["ms"] * 1e3 / max(gm["launches"], 1), 2),
-                                  "gemm_tflop": round(gm["flops"] / 1e12, 3),
-                                  "kernel_class_ms": {k: round(v["ms"], 3) for k, v in prof.items()},
-                                  "kernel_class_tflops": {k: round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1) for k, v in prof.items()},
-                                  "kernel_class_algorithmic_GBps": {k: round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1) for k, v in prof.items()}},
-            "whole_step": {"algorithmic_tflop_per_env_step": round(wl.f_alg / 1e12, 4),
-                           "achieved_tflops_per_gpu": round(step_tflops, 1), "frac": round(step_tflops / PEAK_BF16_TFLOPS, 4)},
-        }
+        # --full only: the box's calibration GEMM and the roofline of one instrumented eager pass (a plain run reports them as null)
+        calib = calibration_gemm(dev) if a.full else None
+        roofline = instrumented_roofline(a, wl, value, world) if a.full else None
         line = {
             "metric": "policy steps/sec/node" if getattr(wl, "unit", "policy steps/s") == "policy steps/s" else "System-2 calls/sec/node",
             "value": round(value, 2), "unit": getattr(wl, "unit", "policy steps/s"), "n_gpus": world,
@@ -1105,8 +1188,8 @@ def main():
             line["config"]["schedule_check"] = {"max_abs_diff_vs_single_stream": round(overlap_check[0], 5), "traj_abs_max": round(overlap_check[1], 3)}
         plain = (a.workload == "n1_dual" and a.cadence == "nominal" and not (a.prefix_kv or a.vit_cache or a.lookdown or a.no_graph or a.no_overlap) and
                  a.s2_every == 1 and a.num_history == 3 and a.dit_ffn == 1536)
-        cpu_leg = wl.cpu_baseline if (world == 1 and not a.no_cpu_baseline) else None
-        if world == 1 and plain and not a.no_variants:
+        cpu_leg = wl.cpu_baseline if (a.full and world == 1 and not a.no_cpu_baseline) else None
+        if a.full and world == 1 and plain and not a.no_variants:
             # (before the CPU leg: that one leaves 64 busy host threads behind it, and the variants' steps carry host work)
             line["variants"] = n1_variants(a)
         # the CPU port of the reference path is timed on rank 0 of a single-GPU run only (contract); the key is always present

@@ -11,6 +11,8 @@ micro_batch x subgoals (sample, sub-goal) pairs, the latent-query backward throu
 ONE flat fp32 bucket over RCCL (N > 1) and the fused clip + AdamW launch. Weights are seeded random at the true shapes, inputs
 synthetic and resident in HBM. The reference trains with per-device batch 2 (train_dual_system.sh:23); global batch = 2 x N x
 accumulation, which does not change the per-sample cost measured here ("scaling": "weak").
+A plain run times the steps and prints the line ("roofline" and "cpu_baseline" null); --full adds the instrumented roofline pass and
+the CPU baseline after the timed region.
 """
 from __future__ import annotations
 
@@ -52,6 +54,9 @@ def parse():
     ap.add_argument("--no-priority", action="store_true", help="A/B: the step's own launches on the caller's stream instead of a high-priority one")
     ap.add_argument("--no-split-prefill", action="store_true", help="A/B: the frozen prefix as one launch sequence instead of two half micro-batches on two streams")
     ap.add_argument("--no-graph-s1", action="store_true", help="System-1 loss + backward as eager launches (round-3 path) instead of one hipGraph replay")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also the instrumented roofline pass and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and the updated trainable fp32 parameters (fixed seeded sample) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -113,13 +118,40 @@ def flops_per_step(qcfg, S, B, T, F):
     return dict(s2_forward=f2, s1_forward=fwd_s1, s1_total=3 * fwd_s1, llm_rows=llm_rows, total=f2 + 3 * fwd_s1 + llm_rows)
 
 
+def instrumented_roofline(tr, batch, qcfg, info, a, dt):
+    """--full: one instrumented eager forward / backward with HIP events around every launch"""
+    from internnav_amd import runtime
+
+    fl = flops_per_step(qcfg, info["S"], info["B"], info["T"], info["F"])
+    runtime.prof_enable(True)
+    tr.graph_prefix = False           # the instrumented pass times every launch of the prefix with HIP events: eager
+    tr.forward_backward(batch)
+    torch.cuda.synchronize()
+    prof = runtime.prof_read()
+    per_kernel = runtime.prof_read_gemm_kernels()
+    runtime.prof_enable(False)
+    tr.P.zero_grad()
+    dom_name, dom = max(per_kernel.items(), key=lambda kv: kv[1]["ms"]) if per_kernel else ("none", dict(ms=0.0, launches=0, flops=0.0))
+    achieved = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
+    step_tflops = fl["total"] * a.steps / dt / 1e12
+    return {"bound": "mfma", "kernel": dom_name, "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "launches": dom["launches"],
+            "avg_launch_us": round(dom["ms"] * 1e3 / max(dom["launches"], 1), 2), "traffic": None,
+            "kernel_class_ms": {k: round(v["ms"], 3) for k, v in prof.items()},
+            "kernel_class_launches": {k: v["launches"] for k, v in prof.items()},
+            "whole_step": {"algorithmic_tflop": {k: round(v / 1e12, 3) for k, v in fl.items()}, "achieved_tflops_per_gpu": round(step_tflops, 1),
+                           "frac": round(step_tflops / PEAK_BF16_TFLOPS, 4)}}
+
+
 def cpu_baseline(info, qcfg):
     """bounded CPU sample of the same step with torch autograd on the oracle (fp32 and bf16 autocast, the faster is reported)."""
     from internnav_amd import synthetic
     from oracle import qwen_vl as o_q  # cpu_baseline leg only
     from oracle import sft as o_sft
 
-    cores = min(64, os.cpu_count() or 1)
+    from bench import cpu_cores
+
+    cores = cpu_cores()
     torch.set_num_threads(cores)
     sd = {k: v.float().requires_grad_(True) for k, v in synthetic.materialize(synthetic.n1_nextdit_spec(), 0).items()}
     g = torch.Generator().manual_seed(0)
@@ -226,19 +258,12 @@ def main():
         dist.broadcast(ref, src=0)
         assert torch.equal(chk, ref), "ranks diverged: the reduced gradients / updates differ"
     value = world * info["B"] * a.steps / dt
+    if rank == 0 and a.dump_outputs:
+        from bench import write_outputs
+
+        write_outputs(a.dump_outputs, {"loss": losses[-1].reshape(1), "params_fp32": tr.P.p32})
     if rank == 0:
-        fl = flops_per_step(qcfg, info["S"], info["B"], info["T"], info["F"])
-        runtime.prof_enable(True)
-        tr.graph_prefix = False           # the instrumented pass times every launch of the prefix with HIP events: eager
-        tr.forward_backward(batch)
-        torch.cuda.synchronize()
-        prof = runtime.prof_read()
-        per_kernel = runtime.prof_read_gemm_kernels()
-        runtime.prof_enable(False)
-        tr.P.zero_grad()
-        dom_name, dom = max(per_kernel.items(), key=lambda kv: kv[1]["ms"]) if per_kernel else ("none", dict(ms=0.0, launches=0, flops=0.0))
-        achieved = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
-        step_tflops = fl["total"] * a.steps / dt / 1e12
+        roofline = instrumented_roofline(tr, batch, qcfg, info, a, dt) if a.full else None
         line = {
             "metric": "SFT samples/sec/node", "value": round(value, 3), "unit": "samples/s", "n_gpus": world,
             "rccl_ranks": int(dist.get_world_size()) if dist is not None else 1, "dist_backend": str(dist.get_backend()) if dist is not None else None, "steps": a.steps, "warmup": a.warmup,
@@ -251,15 +276,9 @@ def main():
                                  ("System-1 loss + backward as one hipGraph replay" if not a.no_graph_s1 else "eager") +
                                  ("; frozen prefix as one hipGraph replay per prompt geometry" if not getattr(a, "no_graph_prefix", False) else "") +
                                  ("; the step's own launches on a high-priority stream" if pipe and not getattr(a, "no_priority", False) else ""), "device": arch, "final_loss": round(float(losses[-1].item()), 5)},
-            "roofline": {"bound": "mfma", "kernel": dom_name, "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "launches": dom["launches"],
-                         "avg_launch_us": round(dom["ms"] * 1e3 / max(dom["launches"], 1), 2), "traffic": None,
-                         "kernel_class_ms": {k: round(v["ms"], 3) for k, v in prof.items()},
-                         "kernel_class_launches": {k: v["launches"] for k, v in prof.items()},
-                         "whole_step": {"algorithmic_tflop": {k: round(v / 1e12, 3) for k, v in fl.items()}, "achieved_tflops_per_gpu": round(step_tflops, 1),
-                                        "frac": round(step_tflops / PEAK_BF16_TFLOPS, 4)}},
+            "roofline": roofline,
         }
-        line["cpu_baseline"] = cpu_baseline(info, qcfg) if (world == 1 and not a.no_cpu_baseline) else None
+        line["cpu_baseline"] = cpu_baseline(info, qcfg) if (a.full and world == 1 and not a.no_cpu_baseline) else None
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
