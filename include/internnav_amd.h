@@ -202,9 +202,11 @@ int ina_norm_bf16(const ina_norm_args* args, void* stream);
 /* ---- patchify: NHWC frames -> im2col rows of the ViT patch-embed conv, fused with the input normalisation.
  *      out[(i*gh + py)*gw + px, c*ps*ps + y*ps + x] = (img[i, py*ps+y, px*ps+x, c] - mean[c]) * inv_std[c]   (bf16),
  *      columns >= 3*ps*ps are zero padding. C == 1 replicates the channel 3x (depth frames).
+ *      C == 4, 6, 7 (NavDPNet goal-image / goal-pixel encoders, navdp_backbone.py:316-412): identity normalisation only (mean 0,
+ *      inv_std 1), out[.., c*ps*ps + y*ps + x] = bf16(img[.., c]) for c < C, columns >= C*ps*ps are zero padding.
  *      reference: navdp_backbone.py:155-181,258-279 + dinov2_layers/patch_embed.py:151-164 (Conv2d 14x14 stride 14). */
 typedef struct ina_patchify_args {
-    const void* img;        /* f32|bf16 (in_dtype) [n, H, W, C] */
+    const void* img;        /* f32|bf16 (in_dtype) [n, H, W, C], C in {1, 3, 4, 6, 7} */
     void* out;              /* bf16 [n * gh * gw, ldo] */
     float mean[3];
     float inv_std[3];

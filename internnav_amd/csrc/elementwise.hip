@@ -1,5 +1,5 @@
 // Small HBM-bound kernels around the MFMA ops of the System-1 policies (gfx950):
-//   patchify      NHWC frames -> normalised im2col rows of the 14x14/14 patch-embed conv (LDS-staged, coalesced both sides)
+//   patchify      NHWC frames -> normalised im2col rows of the 14x14/14 patch-embed conv (LDS-staged, coalesced both sides); C = 1, 3, 4, 6, 7
 //   embed3        nn.Linear(3, C) + positional table, scattered through a row map (also plain table fill)
 //   head3         final LayerNorm + nn.Linear(C, 3) + DDPM / flow-matching Euler update, one wave per token row
 //   seqpool_head  LayerNorm + mean over the T tokens of a sequence + Linear(C, 1)   (NavDP critic)
@@ -46,6 +46,38 @@ __global__ __launch_bounds__(256) void patchify_kernel(PatchifyArgs p) {
             v = (band[y * rowlen + (px * p.ps + x) * p.C + cs] - p.mean[c]) * p.inv_std[c];
         }
         out[i] = (bf16)v;
+    }
+}
+
+// C = 4, 6, 7 (the goal-image / goal-pixel encoders of NavDPNet): identity normalisation, so the band is staged as bf16 - the value
+// written is bf16(img) either way, and a 14 x 224 x 7 band takes 43 KiB instead of the 88 KiB of an f32 one. Columns k = c*ps*ps + y*ps + x
+// up to C*ps*ps, then zero padding up to ldo.
+template <bool IN_F32>
+__global__ __launch_bounds__(256) void patchify_wide_kernel(PatchifyArgs p) {
+    extern __shared__ bf16 band16[];  // [ps][W*C]
+    const int gw = p.W / p.ps, gh = p.H / p.ps;
+    const int img = blockIdx.x / gh, py = blockIdx.x % gh;
+    const int rowlen = p.W * p.C;
+    const int nband = p.ps * rowlen;
+    const size_t base = ((size_t)img * p.H + (size_t)py * p.ps) * rowlen;
+    for (int i = threadIdx.x; i < nband; i += 256) {
+        if (IN_F32) band16[i] = (bf16)reinterpret_cast<const float*>(p.img)[base + i];
+        else band16[i] = reinterpret_cast<const bf16*>(p.img)[base + i];
+    }
+    __syncthreads();
+    const int pp = p.ps * p.ps;
+    const int kreal = p.C * pp;
+    bf16* out = reinterpret_cast<bf16*>(p.out) + ((size_t)img * gh * gw + (size_t)py * gw) * p.ldo;
+    const int total = gw * p.ldo;
+    for (int i = threadIdx.x; i < total; i += 256) {
+        const int px = i / p.ldo, k = i % p.ldo;
+        bf16 v = (bf16)0.f;
+        if (k < kreal) {
+            const int c = k / pp, r = k % pp;
+            const int y = r / p.ps, x = r % p.ps;
+            v = band16[y * rowlen + (px * p.ps + x) * p.C + c];
+        }
+        out[i] = v;
     }
 }
 
@@ -372,14 +404,23 @@ int ina_launch_pool_act(const PoolActArgs& p_in, hipStream_t stream) {
 
 int ina_launch_patchify(const PatchifyArgs& p, hipStream_t stream) {
     INA_REQUIRE(p.n > 0 && p.ps > 0 && p.H % p.ps == 0 && p.W % p.ps == 0, "patchify: bad geometry n=%d H=%d W=%d ps=%d", p.n, p.H, p.W, p.ps);
-    INA_REQUIRE(p.C == 3 || p.C == 1, "patchify: C must be 3 or 1 (got %d)", p.C);
-    INA_REQUIRE(p.ldo >= 3 * p.ps * p.ps && p.ldo % 8 == 0, "patchify: ldo=%d must be >= 3*ps*ps and a multiple of 8", p.ldo);
-    const size_t lds = (size_t)p.ps * p.W * p.C * sizeof(float);
+    INA_REQUIRE(p.C == 1 || p.C == 3 || p.C == 4 || p.C == 6 || p.C == 7, "patchify: C must be 1, 3, 4, 6 or 7 (got %d)", p.C);
+    const bool wide = p.C > 3;
+    if (wide) {
+        for (int c = 0; c < 3; ++c)
+            INA_REQUIRE(p.mean[c] == 0.f && p.inv_std[c] == 1.f, "patchify: C=%d takes no normalisation (mean 0, std 1)", p.C);
+    }
+    const int kreal = (wide ? p.C : 3) * p.ps * p.ps;
+    INA_REQUIRE(p.ldo >= kreal && p.ldo % 8 == 0, "patchify: ldo=%d must be >= %d (C*ps*ps, 3*ps*ps for C <= 3) and a multiple of 8", p.ldo, kreal);
+    const size_t lds = (size_t)p.ps * p.W * p.C * (wide ? sizeof(bf16) : sizeof(float));
     INA_REQUIRE(lds <= 64 * 1024, "patchify: band of %zu bytes does not fit LDS", lds);
     dim3 grid(p.n * (p.H / p.ps));
     InaProfScope prof(INA_PROF_ELEMENTWISE, 0.0, (double)p.n * p.H * p.W * p.C * (p.in_dtype == INA_DT_F32 ? 4.0 : 2.0) +
                       2.0 * p.n * (p.H / p.ps) * (p.W / p.ps) * p.ldo, stream);
-    if (p.in_dtype == INA_DT_F32) hipLaunchKernelGGL(patchify_kernel<true>, grid, dim3(256), lds, stream, p);
+    if (wide) {
+        if (p.in_dtype == INA_DT_F32) hipLaunchKernelGGL(patchify_wide_kernel<true>, grid, dim3(256), lds, stream, p);
+        else hipLaunchKernelGGL(patchify_wide_kernel<false>, grid, dim3(256), lds, stream, p);
+    } else if (p.in_dtype == INA_DT_F32) hipLaunchKernelGGL(patchify_kernel<true>, grid, dim3(256), lds, stream, p);
     else hipLaunchKernelGGL(patchify_kernel<false>, grid, dim3(256), lds, stream, p);
     INA_HIP_CHECK(hipGetLastError());
     return 0;

@@ -136,3 +136,17 @@ def unet1d_flops_per_env(cfg) -> dict:
     film = 2.0 * cfg["global_cond_dim"] * 2 * (2 * d[0] + 2 * d[1] + 2 * d[2] + 2 * d[2] + 2 * d[1] + 2 * d[0])
     total = cfg["num_inference_steps"] * S * f + film
     return dict(forward_per_sequence=f, film=film, total=total)
+
+
+def navdpnet_train_flops(cfg, B: int, pixel_channel: int = 4) -> dict:
+    """one NavDPNet training step (NavDPNet.forward + backward, navdp_policy.py:187-273) on B samples: the frozen RGB ViT-S runs forward
+    only, everything else forward + backward (= 3x its forward: the input and the weight gradient GEMMs)."""
+    M, T, D, depth = cfg["memory_size"], cfg["predict_size"], cfg["token_dim"], cfg["temporal_depth"]
+    Lc = M * 16 + 4
+    rgb = B * M * vit_s_flops()
+    towers = 3 * B * (vit_s_flops() + vit_s_flops(patch_k=6 * 196) + vit_s_flops(patch_k=pixel_channel * 196))
+    former = 3 * B * former_flops(M * 16, (M + 1) * 256, out_dim=D)
+    decoder = 3 * 2 * (denoiser_pass_flops(B, T, Lc, causal=True, d=D, depth=depth) + denoiser_pass_flops(B, T, Lc - 4, causal=False, d=D, depth=depth))
+    cond_kv = 3 * depth * 2 * 2 * B * Lc * D * 2 * D
+    total = rgb + towers + former + decoder + cond_kv
+    return dict(rgb=rgb, towers=towers, former=former, decoder=decoder, cond_kv=cond_kv, total=total)

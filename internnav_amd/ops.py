@@ -291,7 +291,8 @@ def norm(x: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[t
 
 
 def patchify(img: torch.Tensor, out: torch.Tensor, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), ps: int = 14) -> torch.Tensor:
-    """img [n, H, W, C] (f32|bf16, C = 3 or 1) -> out bf16 [n * (H/ps) * (W/ps), ldo] im2col rows (k = c*ps*ps + y*ps + x)."""
+    """img [n, H, W, C] (f32|bf16, C in 1, 3, 4, 6, 7) -> out bf16 [n * (H/ps) * (W/ps), ldo] im2col rows (k = c*ps*ps + y*ps + x; C = 1 is
+    replicated to 3 channels; C > 3 takes mean 0 / std 1 only)."""
     assert img.is_contiguous() and img.dim() == 4 and out.dtype == torch.bfloat16 and out.stride(1) == 1
     a = _lib.PatchifyArgs()
     a.img, a.out = img.data_ptr(), out.data_ptr()

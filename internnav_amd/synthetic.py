@@ -286,6 +286,22 @@ def navdpnet_spec(cfg=NAVDPNET_CFG) -> Spec:
     return s
 
 
+def navdpnet_train_spec(cfg=NAVDPNET_CFG, pixel_channel: int = 4) -> Spec:
+    """The full NavDPNet parameter set (navdp_policy.py:67-133): `navdpnet_spec` plus the image-goal encoder (a ViT-S with a 6-channel
+    patch embed, navdp_backbone.py:316-338), the pixel-goal encoder (`pixel_channel` input channels, :365-389) and the two aux heads -
+    what NavDPNet.forward (:187-273) trains."""
+    s = dict(navdpnet_spec(cfg))
+    D = cfg["token_dim"]
+    for enc, tower, cin in (("image_encoder.", "imagegoal_encoder.", 6), ("pixel_encoder.", "pixelgoal_encoder.", pixel_channel)):
+        vit = dinov2_vits_spec(enc + tower)
+        vit[enc + tower + "patch_embed.proj.weight"] = ((384, cin, 14, 14), "w")
+        s.update(vit)
+        _lin(s, enc + "project_layer", D, 384)
+    _lin(s, "pixel_aux_head", 3, D, kind="w_small")
+    _lin(s, "image_aux_head", 3, D, kind="w_small")
+    return s
+
+
 def n1_navdp_spec(cfg=N1_NAVDP_CFG) -> Spec:
     """NavDP_Policy_DPT_CriticSum_DAT parameters on the navdp_async inference path (internvla_n1/navdp.py:52-108)."""
     D, M, T, V = cfg["token_dim"], cfg["memory_size"], cfg["predict_size"], cfg["vlm_token_dim"]
@@ -573,6 +589,10 @@ def qwen_lookdown_inputs(cfg=QWEN_TEST_CFG):
 
 def navdpnet_state_dict(seed: int = 0, cfg=NAVDPNET_CFG):
     return materialize(navdpnet_spec(cfg), seed)
+
+
+def navdpnet_train_state_dict(seed: int = 0, cfg=NAVDPNET_CFG, pixel_channel: int = 4):
+    return materialize(navdpnet_train_spec(cfg, pixel_channel), seed)
 
 
 def n1_navdp_state_dict(seed: int = 0, cfg=N1_NAVDP_CFG):
