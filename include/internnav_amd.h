@@ -38,7 +38,7 @@ int ina_abi_version(void);
 const char* ina_last_error(void);
 /* Fails (non-zero) unless a gfx950 device is current; fills name[0..n) with the arch string. */
 int ina_device_check(char* name, int n);
-/* sizeof() of the k-th argument struct below (0 gemm, 1 attn, 2 norm, 3 patchify, 4 embed3, 5 head3, 6 seqpool, 7 select, 8 pool_act, 9 gather, 10 rope, 11 mrope_table, 12 argmax, 13 dit_attn, 14 resize_u8, 15 qwen_patchify, 16 u8_lut, 17 resize_f32, 18 gn_mish, 19 pad_rows, 20 ddim_step, 21 ew, 22 colsum, 23 norm_bwd, 24 transpose, 25 sparse_rows, 26 small_linear, 27 mse, 28 adamw, 29 gemm_nn, 30 attn_bwd, 31 dit_rowchain):
+/* sizeof() of the k-th argument struct below (0 gemm, 1 attn, 2 norm, 3 patchify, 4 embed3, 5 head3, 6 seqpool, 7 select, 8 pool_act, 9 gather, 10 rope, 11 mrope_table, 12 argmax, 13 dit_attn, 14 resize_u8, 15 qwen_patchify, 16 u8_lut, 17 resize_f32, 18 gn_mish, 19 pad_rows, 20 ddim_step, 21 ew, 22 colsum, 23 norm_bwd, 24 transpose, 25 sparse_rows, 26 small_linear, 27 mse, 28 adamw, 29 gemm_nn, 30 attn_bwd, 31 dit_rowchain, 32 gemm_dw):
  * lets a binding verify its struct mirrors against the compiled layout. */
 int ina_struct_size(int k);
 /* Per-launch timing for the benchmark's roofline line: while enabled every launch is bracketed by a hipEvent pair on its
@@ -228,6 +228,21 @@ typedef struct ina_embed3_args {
     int32_t out_dtype, x_div;   /* x row = r / x_div (0 means 1): broadcast one vector to x_div consecutive rows */
 } ina_embed3_args;
 int ina_embed3(const ina_embed3_args* args, void* stream);
+
+/* ---- goal_slots: the goal rows of the NavDPNet condition for B envs with goals of mixed kinds, one launch
+ *      reference: NavDPNet.predict_noise writes one goal embedding into condition slots 1..3 (navdp_policy.py:159-170); the embedding is
+ *      point_encoder(goal) or ImageGoalBackbone / PixelGoalBackbone.forward (navdp_backbone.py:340-346, 391-397).
+ *  env b, kind[b]:  0 none   e = 0
+ *                   1 point  e = point_w [D,3] . point[row[b]] + point_b
+ *                   2 image  e = image_w [D,E] . mean_{t < ntok} image_tok[row[b]*ntok + t] + image_b   (fp32 mean of the tower's f32 tokens)
+ *                   3 pixel  the same with the pixel_* operands
+ *  Y[b*L + slot0 + j] = e + P[slot0 + j] for j < nslots (Y bf16|f32 per y_dtype, row stride ldy; P f32 [>= slot0 + nslots, D] or NULL);
+ *  embed (f32 [B, D] or NULL) receives e. row[b] indexes the compact input of its kind (n_point / n_image / n_pixel rows); the caller
+ *  validates the plan - an entry outside it yields NaN rows, never an out-of-bounds read. Plain arguments: no struct, no ABI bump. */
+int ina_goal_slots(void* Y, int32_t ldy, int32_t y_dtype, int32_t L, int32_t slot0, int32_t nslots, const float* P, int32_t B, int32_t D,
+                   const int32_t* kind, const int32_t* row, float* embed, const float* point, int32_t n_point, const float* point_w,
+                   const float* point_b, const float* image_tok, int32_t n_image, const float* image_w, const float* image_b,
+                   const float* pixel_tok, int32_t n_pixel, const float* pixel_w, const float* pixel_b, int32_t ntok, int32_t E, void* stream);
 
 /* ---- head3: final norm + Linear(C, 3) + sampler update, one wave per row.
  *      e = W . (norm(X[r]) * gamma + beta) * (1 + mod_scale[r / mod_div]) ... + b

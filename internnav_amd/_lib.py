@@ -285,6 +285,9 @@ SYMBOLS = {
     "ina_norm_bf16": (C.c_int, [C.POINTER(NormArgs), c_void_p]),
     "ina_patchify": (C.c_int, [C.POINTER(PatchifyArgs), c_void_p]),
     "ina_embed3": (C.c_int, [C.POINTER(Embed3Args), c_void_p]),
+    "ina_goal_slots": (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                 c_void_p, c_int32, c_int32, c_void_p]),
     "ina_head3": (C.c_int, [C.POINTER(Head3Args), c_void_p]),
     "ina_seqpool_head": (C.c_int, [C.POINTER(SeqpoolArgs), c_void_p]),
     "ina_select_traj": (C.c_int, [C.POINTER(SelectArgs), c_void_p]),

@@ -162,6 +162,14 @@ int ina_gemm_preshuffle(const void* W, void* Wp, int32_t N, int32_t K, int64_t l
     return ina_launch_gemm_preshuffle(W, Wp, N, K, (long)ldw, reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_goal_slots(void* Y, int32_t ldy, int32_t y_dtype, int32_t L, int32_t slot0, int32_t nslots, const float* P, int32_t B, int32_t D,
+                   const int32_t* kind, const int32_t* row, float* embed, const float* point, int32_t n_point, const float* point_w,
+                   const float* point_b, const float* image_tok, int32_t n_image, const float* image_w, const float* image_b,
+                   const float* pixel_tok, int32_t n_pixel, const float* pixel_w, const float* pixel_b, int32_t ntok, int32_t E, void* stream) {
+    return ina_launch_goal_slots(Y, ldy, y_dtype, L, slot0, nslots, P, B, D, kind, row, embed, point, n_point, point_w, point_b, image_tok, n_image,
+                                 image_w, image_b, pixel_tok, n_pixel, pixel_w, pixel_b, ntok, E, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_gemm_select(const ina_gemm_args* args, int* kernel) {
     INA_REQUIRE(args != nullptr && kernel != nullptr, "gemm_select: null argument");
     GemmArgs p;

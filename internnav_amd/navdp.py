@@ -3,6 +3,7 @@
 Two engines with the reference's method names and tensor contracts:
   * `NavDPNet`                        <- internnav/model/basemodel/navdp/navdp_policy.py:34  (BASELINE config #2)
         predict_pointgoal_batch_action_vel(goal_point, input_images, input_depths) -> (negative, positive) trajectories
+        (+ the no-goal, image-goal, pixel-goal and mixed-goal siblings: the same sampler with another goal embedding in slots 1..3)
   * `NavDPPolicyDAT` (N1 navdp_async) <- internnav/model/basemodel/internvla_n1/navdp.py:16
         predict_pointgoal_action_async(vlm_tokens, input_images, input_depths) -> all 32 sampled trajectories
 
@@ -30,7 +31,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import ops, synthetic
 from .vit_s import DinoV2Encoder, VitWorkspace
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -237,8 +238,85 @@ class _NavDPBase:
         return sample
 
 
+GOAL_NONE, GOAL_POINT, GOAL_IMAGE, GOAL_PIXEL = 0, 1, 2, 3
+"""goal kinds of predict_mixedgoal_batch_action_vel (the codes ina_goal_slots reads)."""
+GOAL_TOWERS = (("image", "image_encoder.", "imagegoal_encoder."), ("pixel", "pixel_encoder.", "pixelgoal_encoder."))
+"""(kind, module prefix, ViT-S prefix) of ImageGoalBackbone / PixelGoalBackbone in the NavDPNet state dict."""
+
+
+def goal_tower_keys(prefix: str, tower: str):
+    """state-dict keys one goal tower is built from: the ViT-S (its unused `mask_token` aside) and project_layer."""
+    vit = [k for k in synthetic.dinov2_vits_spec(prefix + tower) if not k.endswith("mask_token")]
+    return vit + [prefix + "project_layer.weight", prefix + "project_layer.bias"]
+
+
+class GoalPlan:
+    """Host plan of a mixed-goal call: per env its kind and its row in the compact input of that kind (int32 [B] each), and the row counts
+    of the point / image / pixel inputs."""
+
+    def __init__(self, kind: torch.Tensor, row: torch.Tensor, n_point: int, n_image: int, n_pixel: int):
+        self.kind, self.row = kind, row
+        self.B = kind.numel()
+        self.n_point, self.n_image, self.n_pixel = n_point, n_image, n_pixel
+
+
+def goal_plan(goal_kind, goal_point: Optional[torch.Tensor] = None, goal_image: Optional[torch.Tensor] = None,
+              goal_pixel: Optional[torch.Tensor] = None, pixel_channel: Optional[int] = None, image_channels: int = 6,
+              img_size: int = 224) -> GoalPlan:
+    """Validate the goal arguments of a mixed call against goal_kind and index them (host only, no device work).
+    goal_kind int [B] in {0 none, 1 point, 2 image, 3 pixel}. goal_image [n_image, H, W, image_channels] and goal_pixel
+    [n_pixel, H, W, pixel_channel] hold only the rows of the envs of their kind, in env order. goal_point is either [B, 3] (row b = env b;
+    the rows of other kinds are not read) or compact [n_point, 3]. A tensor for a kind no env has is refused, as is a missing one."""
+    kind = torch.as_tensor(goal_kind)
+    if kind.dim() != 1 or kind.numel() == 0 or kind.dtype.is_floating_point or kind.dtype == torch.bool:
+        raise ValueError(f"goal_kind must be a non-empty 1-D integer tensor, got {tuple(kind.shape)} {kind.dtype}")
+    kind = kind.to(torch.int64).cpu()
+    if bool(((kind < GOAL_NONE) | (kind > GOAL_PIXEL)).any()):
+        raise ValueError(f"goal_kind values must be 0 (none), 1 (point), 2 (image) or 3 (pixel), got {sorted(set(kind.tolist()))}")
+    B = kind.numel()
+    row = torch.zeros(B, dtype=torch.int64)
+    counts = []
+    for code, name, t, shape in ((GOAL_POINT, "goal_point", goal_point, None),
+                                 (GOAL_IMAGE, "goal_image", goal_image, (img_size, img_size, image_channels)),
+                                 (GOAL_PIXEL, "goal_pixel", goal_pixel, (img_size, img_size, pixel_channel))):
+        sel = kind == code
+        n = int(sel.sum())
+        counts.append(n)
+        if n == 0:
+            if t is not None:
+                raise ValueError(f"{name} given but no env has goal kind {code}")
+            continue
+        if t is None:
+            raise ValueError(f"{n} env(s) have goal kind {code} but {name} is None")
+        if code == GOAL_POINT:
+            if tuple(t.shape) not in ((B, 3), (n, 3)):
+                raise ValueError(f"goal_point must be [B, 3] = [{B}, 3] or [n_point, 3] = [{n}, 3], got {tuple(t.shape)}")
+            row[sel] = torch.nonzero(sel).flatten() if t.shape[0] == B else torch.arange(n)
+            continue
+        if shape[2] is None:
+            raise ValueError(f"{name} needs a pixel-goal encoder, and this checkpoint has none")
+        if tuple(t.shape) != (n,) + shape:
+            raise ValueError(f"{name} must be [{n}, {shape[0]}, {shape[1]}, {shape[2]}] (the rows of the {n} env(s) of kind {code}, in env "
+                             f"order), got {tuple(t.shape)}")
+        row[sel] = torch.arange(n)
+    return GoalPlan(kind.to(torch.int32), row.to(torch.int32), *counts)
+
+
+class _GoalTower:
+    """ImageGoalBackbone / PixelGoalBackbone (navdp_backbone.py:316-397): a ViT-S with a C-channel patch embed whose fp32 final-LayerNorm
+    tokens ina_goal_slots averages and projects with project_layer."""
+
+    def __init__(self, sd, prefix: str, tower: str, device):
+        self.vit = DinoV2Encoder(sd, prefix + tower, device)
+        self.proj_w = sd[prefix + "project_layer.weight"].to(device=device, dtype=torch.float32).contiguous()
+        self.proj_b = sd[prefix + "project_layer.bias"].to(device=device, dtype=torch.float32).contiguous()
+        self.channels = self.vit.channels
+
+
 class NavDPNet(_NavDPBase):
-    """MI355X engine behind `NavDPNet.predict_pointgoal_batch_action_vel` (navdp_policy.py:302-321), batched over envs."""
+    """MI355X engine behind `NavDPNet.predict_pointgoal_batch_action_vel` (navdp_policy.py:302-321), batched over envs, and its siblings
+    with no goal, an image goal, a pixel goal or a mix of goal kinds. The image / pixel goal towers are built when the state dict holds
+    them (`pixel_channel` is read off the pixel tower's patch embed); a point-only state dict serves the point and no-goal calls."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: dict, device="cuda:0", max_envs: int = 64):
         device = torch.device(device)
@@ -250,10 +328,31 @@ class NavDPNet(_NavDPBase):
         sd, p = state_dict, "rgbd_encoder."
         self.rgb = DinoV2Encoder(sd, p + "rgb_model.", device)
         self.depth_vit = DinoV2Encoder(sd, p + "depth_model.", device)
-        self.vit_ws = VitWorkspace(max_envs * M, device)
+        self.goal_towers: Dict[str, _GoalTower] = {}
+        self.missing_goal_keys: Dict[str, list] = {}
+        for kind, gp, tower in GOAL_TOWERS:
+            keys = goal_tower_keys(gp, tower)
+            missing = [k for k in keys if k not in sd]
+            if len(missing) == len(keys) and not any(k.startswith(gp) for k in sd):
+                self.missing_goal_keys[kind] = missing          # a point-only checkpoint: the tower is absent, its calls are refused
+                continue
+            if missing:
+                raise KeyError(f"NavDPNet state dict holds part of the {kind}-goal encoder: {len(missing)} of its parameters are missing, "
+                               f"e.g. {missing[:4]}")
+            self.goal_towers[kind] = _GoalTower(sd, gp, tower, device)
+        img = self.goal_towers.get("image")
+        pix = self.goal_towers.get("pixel")
+        assert img is None or img.channels == 6, f"image-goal encoder with a {img.channels}-channel patch embed (ImageGoalBackbone takes 6)"
+        self.pixel_channel = pix.channels if pix is not None else None
+        # the goal towers run over at most max_envs frames: the shared im2col buffer holds the widest of them
+        widest = max([t.vit.kpad for t in self.goal_towers.values()], default=0)
+        self.vit_ws = VitWorkspace(max_envs * M, device, patch_numel=max_envs * 256 * widest)
         self.former = _RGBDFormer(sd, p, device, M * 16, (M + 1) * 256, max_envs, "former_query.position_embedding.weight",
                                   "former_pe.position_embedding.weight")
         f32 = torch.float32
+        if self.goal_towers:   # fp32 final-LayerNorm tokens of the image sub-batch, then the pixel sub-batch (together <= B frames)
+            self.goal_tok = torch.empty(max_envs * 256, 384, dtype=f32, device=device)
+        self.goal_embed = torch.empty(max_envs, cfg["token_dim"], dtype=f32, device=device)   # the last goal call's embeddings
         self.cond_pos = sd["cond_pos_embed.position_embedding.weight"].to(device=device, dtype=f32).contiguous()  # [Lc, D]
         self.out_pos = sd["out_pos_embed.position_embedding.weight"].to(device=device, dtype=f32).contiguous()    # [T, D]
         self.pt_w = sd["point_encoder.weight"].to(device=device, dtype=f32).contiguous()
@@ -321,7 +420,7 @@ class NavDPNet(_NavDPBase):
                                   x_init: torch.Tensor, step_noise: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         B = input_images.shape[0]
         assert B <= self.b_max and (goal_point is None or goal_point.shape[0] == B)
-        S, T, D, Lc = self.S, self.T, self.D, self.Lc
+        Lc = self.Lc
         self.encode_rgbd(B, input_images, input_depths)
         cond = self.cond[: B * Lc]
         for j in (1, 2, 3):  # the goal embedding (point goal, or zeros: table fill) fills the three goal slots (navdp_policy.py:162)
@@ -329,6 +428,11 @@ class NavDPNet(_NavDPBase):
                 ops.embed3(None, None, None, out=cond, pos=self.cond_pos[j:j + 1], rows=B, out_map=(1, Lc, j))
             else:
                 ops.embed3(goal_point, self.pt_w, self.pt_b, out=cond, pos=self.cond_pos[j:j + 1], rows=B, out_map=(1, Lc, j))
+        return self._sample_and_rank(B, x_init, step_noise)
+
+    def _sample_and_rank(self, B: int, x_init: torch.Tensor, step_noise: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """cond rows 1.. are filled: the DDPM loop, the critic and the top-8 / bottom-8 selection of every env."""
+        S, T, Lc = self.S, self.T, self.Lc
         sample = self._denoise(B, x_init, step_noise)
         # critic (navdp_policy.py:172-185): no-goal condition with slots 0..3 masked -> the K/V of cond rows 4.. are reused,
         # rows 0..3 are excluded by kv_start = 4 (memory_mask), no causal mask.
@@ -339,6 +443,66 @@ class NavDPNet(_NavDPBase):
         ops.seqpool_head(self.ws.x[:rows], T, self.ln_w, self.ln_b, self.cr_w, self.cr_b, self.critic[: B * S], eps=1e-5)
         ops.select_traj(self.critic[: B * S].view(B, S), sample.view(B, S, T, 3), self.neg[:B], self.pos[:B], k=8, scale=0.25)
         return self.neg[:B], self.pos[:B]
+
+    def predict_imagegoal_batch_action_vel(self, goal_image: torch.Tensor, input_images: torch.Tensor, input_depths: torch.Tensor,
+                                           x_init: torch.Tensor, step_noise: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """the point-goal call with goal_embed = image_encoder(goal_image) (ImageGoalBackbone, navdp_backbone.py:316-346). goal_image f32
+        [B,224,224,6] in 0..1: the goal RGB then the current RGB (navdp_lerobot_dataset.py:497-503). Other arguments and the result as
+        predict_pointgoal_batch_action_vel."""
+        kind = torch.full((goal_image.shape[0],), GOAL_IMAGE, dtype=torch.int32)
+        return self.predict_mixedgoal_batch_action_vel(kind, goal_image=goal_image, input_images=input_images, input_depths=input_depths,
+                                                       x_init=x_init, step_noise=step_noise)
+
+    def predict_pixelgoal_batch_action_vel(self, goal_pixel: torch.Tensor, input_images: torch.Tensor, input_depths: torch.Tensor,
+                                           x_init: torch.Tensor, step_noise: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """the point-goal call with goal_embed = pixel_encoder(goal_pixel) (PixelGoalBackbone, navdp_backbone.py:365-397). goal_pixel f32
+        [B,224,224,pixel_channel] in 0..1: RGB then the goal mask (4 channels), + the current RGB (7; navdp_lerobot_dataset.py:511-523)."""
+        kind = torch.full((goal_pixel.shape[0],), GOAL_PIXEL, dtype=torch.int32)
+        return self.predict_mixedgoal_batch_action_vel(kind, goal_pixel=goal_pixel, input_images=input_images, input_depths=input_depths,
+                                                       x_init=x_init, step_noise=step_noise)
+
+    def predict_mixedgoal_batch_action_vel(self, goal_kind, goal_point: Optional[torch.Tensor] = None, goal_image: Optional[torch.Tensor] = None,
+                                           goal_pixel: Optional[torch.Tensor] = None, *, input_images: torch.Tensor, input_depths: torch.Tensor,
+                                           x_init: torch.Tensor, step_noise: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """B envs with goals of different kinds in one call. goal_kind int [B]: 0 none, 1 point, 2 image, 3 pixel. goal_image
+        [n_image,224,224,6] and goal_pixel [n_pixel,224,224,pixel_channel] hold only the rows of the envs of that kind, in env order;
+        goal_point is [B,3] or [n_point,3] (see goal_plan). Each goal tower runs once over its sub-batch, ina_goal_slots fills the goal
+        slots of every env in one launch, and the RGB-D encoder, the sampler, the critic and the ranking run once over all B envs.
+        -> (negative, positive) f32 [B,8,T,3]; the goal embeddings stay in self.goal_embed[:B]."""
+        kinds = torch.as_tensor(goal_kind)
+        for code, kind in ((GOAL_IMAGE, "image"), (GOAL_PIXEL, "pixel")):
+            if kind not in self.goal_towers and bool((kinds == code).any()):
+                miss = self.missing_goal_keys[kind]
+                raise KeyError(f"this NavDPNet checkpoint has no {kind}-goal encoder: {len(miss)} parameters are missing, e.g. {miss[:4]}")
+        plan = goal_plan(kinds, goal_point, goal_image, goal_pixel, pixel_channel=self.pixel_channel)
+        B = plan.B
+        if not (B <= self.b_max and input_images.shape[0] == B and x_init.shape[0] == B and step_noise.shape[1] == B):
+            raise ValueError(f"{B} goal kinds, {input_images.shape[0]} image stacks, {x_init.shape[0]} x_init rows, "
+                             f"{step_noise.shape[1]} step-noise rows (engine built for up to {self.b_max} envs)")
+        dev = self.device
+        plan_dev = torch.cat([plan.kind, plan.row]).pin_memory().to(dev, non_blocking=True)
+        self.encode_rgbd(B, input_images, input_depths)
+        self.encode_goals(plan, plan_dev, goal_point, goal_image, goal_pixel)
+        return self._sample_and_rank(B, x_init, step_noise)
+
+    def encode_goals(self, plan: GoalPlan, plan_dev: torch.Tensor, goal_point, goal_image, goal_pixel):
+        """goal towers over their compact sub-batches (fp32 tokens into self.goal_tok), then cond rows 1..3 of every env (+ cond_pos_embed)
+        and self.goal_embed in one ina_goal_slots launch. plan_dev: int32 [2B] = plan.kind | plan.row on the device."""
+        B, Lc, dev = plan.B, self.Lc, self.device
+        towers, r0 = {}, 0
+        for kind, frames, n in (("image", goal_image, plan.n_image), ("pixel", goal_pixel, plan.n_pixel)):
+            if not n:
+                continue
+            t = self.goal_towers[kind]
+            tok = self.goal_tok[r0 * 256:(r0 + n) * 256]
+            t.vit.forward(frames.to(dev).contiguous(), self.vit_ws, None, extra_outputs=((None, tok, None, None),))
+            towers[kind] = (tok, t.proj_w, t.proj_b, 256)
+            r0 += n
+        point = None
+        if plan.n_point:
+            point = (goal_point.to(device=dev, dtype=torch.float32).contiguous(), self.pt_w, self.pt_b)
+        ops.goal_slots(self.cond[: B * Lc], Lc, plan_dev[:B], plan_dev[B:], pos=self.cond_pos, embed=self.goal_embed[:B], point=point,
+                       image=towers.get("image"), pixel=towers.get("pixel"))
 
 
 class NavDPPolicyDAT(_NavDPBase):

@@ -330,6 +330,40 @@ def embed3(x: Optional[torch.Tensor], w: Optional[torch.Tensor], bias: Optional[
     return out
 
 
+def goal_slots(out: torch.Tensor, L: int, kind: torch.Tensor, row: torch.Tensor, pos: Optional[torch.Tensor] = None, slot0: int = 1,
+               nslots: int = 3, embed: Optional[torch.Tensor] = None, point=None, image=None, pixel=None) -> torch.Tensor:
+    """goal embedding e of every env b by its kind (0 none: 0, 1 point: w @ point[row[b]] + bias, 2 image / 3 pixel: w @ mean of the
+    tower tokens tok[row[b]*ntok : (row[b]+1)*ntok] + bias) -> out[b*L + slot0 + j] = e + pos[slot0 + j] (j < nslots); embed f32 [B, D]
+    receives e. kind / row: int32 [B] on the device. point = (x f32 [n, 3], w f32 [D, 3], bias f32 [D]); image / pixel = (tok f32
+    [n * ntok, E], w f32 [D, E], bias f32 [D], ntok); n = rows of that input (0 or None: the kind is absent)."""
+    o2 = _as2d(out)
+    B, D = kind.numel(), o2.shape[1]
+    assert kind.dtype == row.dtype == torch.int32 and kind.is_contiguous() and row.is_contiguous() and row.numel() == B
+    assert o2.shape[0] >= B * L and (embed is None or (embed.dtype == torch.float32 and embed.is_contiguous() and embed.numel() >= B * D))
+    assert pos is None or (pos.dtype == torch.float32 and pos.is_contiguous() and pos.shape[-1] == D and pos.numel() >= (slot0 + nslots) * D)
+    px, pw, pb, n_point = None, None, None, 0
+    if point is not None:
+        x, w, b = point
+        assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[-1] == 3 and w.shape == (D, 3)
+        px, pw, pb, n_point = x, _f32(w), _f32(b), x.numel() // 3
+    towers, ntok, E = [], 0, 0
+    for t in (image, pixel):
+        if t is None:
+            towers.append((None, None, None, 0))
+            continue
+        tok, w, b, nt = t
+        assert tok.dtype == torch.float32 and tok.is_contiguous() and tok.dim() == 2 and tok.shape[0] % nt == 0 and w.shape == (D, tok.shape[1])
+        assert (ntok, E) in ((0, 0), (nt, tok.shape[1])), "image and pixel towers must agree on tokens per frame and width"
+        ntok, E = nt, tok.shape[1]
+        towers.append((tok, _f32(w), _f32(b), tok.shape[0] // nt))
+    (it, iw, ib, n_image), (qt, qw, qb, n_pixel) = towers
+    rc = _lib.lib().ina_goal_slots(o2.data_ptr(), o2.stride(0), _DT[o2.dtype], L, slot0, nslots, _ptr(pos), B, D, kind.data_ptr(),
+                                   row.data_ptr(), _ptr(embed), _ptr(px), n_point, _ptr(pw), _ptr(pb), _ptr(it), n_image, _ptr(iw),
+                                   _ptr(ib), _ptr(qt), n_pixel, _ptr(qw), _ptr(qb), ntok, E, _stream())
+    _lib.check(rc, "goal_slots")
+    return out
+
+
 def head3(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, gamma=None, beta=None, eps: float = 1e-5, mode: int = 0,
           sample: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, eps_out: Optional[torch.Tensor] = None,
           coef=(0.0, 0.0, 0.0, 0.0, 0.0), clip: float = 1.0, mod_scale: Optional[torch.Tensor] = None, mod_div: int = 1):

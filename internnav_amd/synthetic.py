@@ -269,8 +269,9 @@ N1_NAVDP_CFG = dict(image_size=224, memory_size=2, predict_size=32, temporal_dep
 
 
 def navdpnet_spec(cfg=NAVDPNET_CFG) -> Spec:
-    """NavDPNet parameters used by the point-goal inference path (navdp_policy.py:67-133); the image/pixel goal encoders
-    and aux heads exist in the reference module but are not on this path and are left at their own initialisation."""
+    """NavDPNet parameters of the point-goal and no-goal inference paths (navdp_policy.py:67-133): a point-only checkpoint. The image /
+    pixel goal encoders (which the engine's image-, pixel- and mixed-goal calls need) and the aux heads are left out - the reference
+    module keeps its own initialisation for them; `navdpnet_train_spec` is the full set."""
     D, M, T = cfg["token_dim"], cfg["memory_size"], cfg["predict_size"]
     s: Spec = {}
     s.update(rgbd_backbone_spec("rgbd_encoder.", M, D, dat=False))
@@ -611,6 +612,24 @@ def navdpnet_inputs(B: int, seed: int = 0, cfg=NAVDPNET_CFG):
     x_init = torch.randn(B, S, T, 3, generator=g)
     step_noise = torch.randn(K, B, S, T, 3, generator=g)
     return dict(goal=goal, images=images, depths=depths, x_init=x_init, step_noise=step_noise)
+
+
+def navdpnet_goal_inputs(B: int, seed: int = 0, pixel_channel: int = 4):
+    """Seeded image / pixel goals at the navdp_collate_fn layout (f32 NHWC 224 x 224 in 0..1): goal_image [B,224,224,6] = goal RGB, current
+    RGB (navdp_lerobot_dataset.py:497-503); goal_pixel [B,224,224,pixel_channel] = RGB, a rectangular goal mask (1 inside), and for 7
+    channels the current RGB (:511-523)."""
+    assert pixel_channel in (4, 7), f"pixel_channel {pixel_channel}: the reference uses 4 or 7"
+    g = torch.Generator().manual_seed(3000 + seed)
+    goal_image = torch.rand(B, 224, 224, 6, generator=g)
+    rgb = torch.rand(B, 224, 224, 3, generator=g)
+    mask = torch.zeros(B, 224, 224, 1)
+    corners = torch.randint(0, 160, (B, 2), generator=g)
+    sizes = torch.randint(16, 64, (B, 2), generator=g)
+    for b in range(B):
+        (y, x), (h, w) = corners[b].tolist(), sizes[b].tolist()
+        mask[b, y:y + h, x:x + w] = 1.0
+    parts = [rgb, mask] + ([torch.rand(B, 224, 224, 3, generator=g)] if pixel_channel == 7 else [])
+    return dict(goal_image=goal_image, goal_pixel=torch.cat(parts, dim=-1))
 
 
 def n1_navdp_inputs(B: int, seed: int = 0, cfg=N1_NAVDP_CFG):

@@ -7,7 +7,9 @@ dinov2_layers/block.py:82-107, attention.py:49-62, patch_embed.py:151-164) with 
 libinternnav_amd.so. State-dict keys are the reference's, so a real `depth_anything_v2_vits.pth` loads unchanged.
 
 Data layout in HBM (n = frames in the batch):
-  patches  bf16 [n*256, 592]   im2col rows, k = c*196 + y*14 + x, 4 zero pad columns (K multiple of 8 for the MFMA GEMM)
+  patches  bf16 [n*256, kpad]  im2col rows, k = c*196 + y*14 + x, zero pad columns up to kpad = max(C, 3)*196 rounded up to a multiple
+                               of 8 for the MFMA GEMM (592 for the RGB / depth towers, 1176 / 784 / 1376 for the 6- / 4- / 7-channel
+                               goal towers of NavDPNet); the buffer is shared, each encoder views it at its own row width
   x        f32  [n*257, 384]   residual stream (cls + 256 patch tokens per frame), updated in place by GEMM epilogues
   h / att  bf16 [n*257, 384]   LayerNorm output / attention output (GEMM A operands)
   qkv      bf16 [n*257, 1152]  fused q|k|v, read by the attention kernel through strided views (no split copies)
@@ -27,6 +29,12 @@ D, DEPTH, HEADS, HD, PATCH = 384, 12, 6, 64, 14
 KPAD = 592  # 3*14*14 = 588 padded to a multiple of 8
 
 
+def patch_kpad(channels: int) -> int:
+    """im2col row width of a patch-embed conv weight [384, channels, 14, 14] (the rule of sft.DinoTrain): max(C, 3)*196 rounded up to a
+    multiple of 8 - a 1-channel input is replicated to 3 channels."""
+    return (max(channels, 3) * PATCH * PATCH + 7) // 8 * 8
+
+
 def interpolate_pos_embed(pos_embed: torch.Tensor, w: int, h: int, offset: float = 0.1) -> torch.Tensor:
     """Input-independent bicubic resampling of the 37x37 positional grid (dinov2.py:180-211); done once on the host at load."""
     N = pos_embed.shape[1] - 1
@@ -43,12 +51,14 @@ def interpolate_pos_embed(pos_embed: torch.Tensor, w: int, h: int, offset: float
 
 
 class VitWorkspace:
-    """Activation buffers for up to `n_max` frames; shared by every ViT-S instance of a policy (they run back to back)."""
+    """Activation buffers for up to `n_max` frames; shared by every ViT-S instance of a policy (they run back to back).
+    patches is a flat bf16 buffer of max(n_max * 256 * KPAD, patch_numel) elements: an encoder of row width kpad views its first
+    n * 256 * kpad elements, so a policy sizes it for the widest tower it holds at the frame count that tower runs at."""
 
-    def __init__(self, n_max: int, device):
+    def __init__(self, n_max: int, device, patch_numel: int = 0):
         bf, f32 = torch.bfloat16, torch.float32
         self.n_max = n_max
-        self.patches = torch.empty(n_max * 256, KPAD, dtype=bf, device=device)
+        self.patches = torch.empty(max(n_max * 256 * KPAD, patch_numel), dtype=bf, device=device)
         self.x = torch.empty(n_max * 257, D, dtype=f32, device=device)
         self.h = torch.empty(n_max * 257, D, dtype=bf, device=device)
         self.att = torch.empty(n_max * 257, D, dtype=bf, device=device)
@@ -66,8 +76,14 @@ class DinoV2Encoder:
         def f(k):
             return sd[prefix + k].to(device=device, dtype=f32).contiguous()
 
-        conv = sd[prefix + "patch_embed.proj.weight"].float().reshape(D, 3 * PATCH * PATCH)
-        self.w_patch = F.pad(conv, (0, KPAD - conv.shape[1])).to(device=device, dtype=bf).contiguous()
+        conv = sd[prefix + "patch_embed.proj.weight"]
+        # 3 (RGB, and depth replicated to 3), 6 (image goal), 4 / 7 (pixel goal); a 1-channel conv reads channel 0 of the replicated
+        # depth im2col (its weight is zero-padded over the two copies)
+        self.channels = int(conv.shape[1])
+        assert tuple(conv.shape) == (D, self.channels, PATCH, PATCH) and self.channels in (1, 3, 4, 6, 7), f"{prefix}: patch embed {tuple(conv.shape)}"
+        self.kpad = patch_kpad(self.channels)
+        conv = conv.float().reshape(D, self.channels * PATCH * PATCH)
+        self.w_patch = F.pad(conv, (0, self.kpad - conv.shape[1])).to(device=device, dtype=bf).contiguous()
         self.b_patch = f("patch_embed.proj.bias")
         pe = interpolate_pos_embed(sd[prefix + "pos_embed"].cpu(), img_size, img_size)
         self.pos = pe[0, 1:].to(device=device, dtype=f32).contiguous()                                   # [256, 384]
@@ -87,18 +103,22 @@ class DinoV2Encoder:
 
     def forward(self, frames: torch.Tensor, ws: VitWorkspace, out: Optional[torch.Tensor], out_map=None,
                 pos: Optional[torch.Tensor] = None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), extra_outputs=()) -> torch.Tensor:
-        """frames [n, 224, 224, C] (C = 3, or 1 replicated to 3 channels; f32 or bf16) -> bf16 patch tokens written to
+        """frames [n, 224, 224, C] (C = the conv's input channels, or 1 replicated to a 3-channel conv; f32 or bf16; C > 3 takes no
+        normalisation) -> bf16 patch tokens written to
         `out` rows out_map(i*256 + p) (+ pos[(i*256+p) % len(pos)]); the cls token is dropped as in the reference.
         extra_outputs: further (out_bf16 | None, out_f32 | None, out_map, pos) destinations of the same final LayerNorm
         (e.g. tokens + a positional table as the fp32 stream of the next module)."""
-        n = frames.shape[0]
+        n, kp = frames.shape[0], self.kpad
         assert n <= ws.n_max and frames.shape[1] == frames.shape[2] == self.img_size
+        assert frames.shape[3] == self.channels or (frames.shape[3] == 1 and self.channels <= 3), \
+            f"{frames.shape[3]}-channel frames into a {self.channels}-channel patch embed"
+        assert n * 256 * kp <= ws.patches.numel(), f"VitWorkspace patches hold {ws.patches.numel()} elements, {n} frames x {kp} need more"
         T = 257
-        patches, x, h, att, qkv, mlp = (ws.patches[: n * 256], ws.x[: n * T], ws.h[: n * T], ws.att[: n * T],
+        patches, x, h, att, qkv, mlp = (ws.patches[: n * 256 * kp].view(n * 256, kp), ws.x[: n * T], ws.h[: n * T], ws.att[: n * T],
                                         ws.qkv[: n * T], ws.mlp[: n * T])
         ops.patchify(frames, patches, mean, std, PATCH)
         x3 = x.view(n, T, D)
-        ops.linear(patches.view(n, 256, KPAD), self.w_patch, bias=self.b_patch, residual=self.pos, out=x3[:, 1:, :], batched=True)
+        ops.linear(patches.view(n, 256, kp), self.w_patch, bias=self.b_patch, residual=self.pos, out=x3[:, 1:, :], batched=True)
         ops.embed3(None, None, None, out=x, pos=self.cls_pos, rows=n, out_map=(1, T, 0))
         qkv5 = qkv.view(n, T, 3, HEADS, HD)
         for b in self.blocks:
