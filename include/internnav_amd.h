@@ -244,6 +244,17 @@ int ina_goal_slots(void* Y, int32_t ldy, int32_t y_dtype, int32_t L, int32_t slo
                    const float* point_b, const float* image_tok, int32_t n_image, const float* image_w, const float* image_b,
                    const float* pixel_tok, int32_t n_pixel, const float* pixel_w, const float* pixel_b, int32_t ntok, int32_t E, void* stream);
 
+/* ---- kv_copy: row ranges of the System-2 KV cache between the engine's cache slots and caller-owned tensors, all layers and sequences
+ *      of a call in ONE launch (a 16-byte vector bit copy, graph capturable).
+ *  layer_base: device int64 [n_layers], address of layer l's cache (rows of row_bytes bytes, engine_rows of them);
+ *  seq: device int64 [n_seq, 4] = { caller address of the sequence's layer-0 first row, caller layer stride in bytes,
+ *       first engine row (slot * S_max + first cached position), n_rows }; the caller side holds n_rows contiguous rows per layer.
+ *  to_engine 0: engine -> caller (export), 1: caller -> engine (import). max_rows >= every n_rows (sizes the grid);
+ *  row_bytes a multiple of 16, every address 16-byte aligned. An entry outside [0, engine_rows) copies nothing.
+ *  Plain arguments: no struct, no ABI bump. */
+int ina_kv_copy(int32_t to_engine, const int64_t* layer_base, int32_t n_layers, const int64_t* seq, int32_t n_seq, int64_t engine_rows,
+                int64_t row_bytes, int64_t max_rows, void* stream);
+
 /* ---- head3: final norm + Linear(C, 3) + sampler update, one wave per row.
  *      e = W . (norm(X[r]) * gamma + beta) * (1 + mod_scale[r / mod_div]) ... + b
  *      mode 0: eps_out[r] = e ; mode 1 (DDPM, diffusers DDPMScheduler.step): x0 = clamp((s - c1 e) c0, +-clip),

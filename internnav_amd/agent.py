@@ -42,6 +42,28 @@ _FATAL = (CapacityError, EngineError, MemoryError, KeyboardInterrupt)
 _PENDING = object()      # marker for "this env's answer is a pixel goal, its latents come with the chunk's generate_latents call"
 
 
+def plan_s2_chunks(lens, reuse, cap: int, s_max: int, tail: int) -> List[List[int]]:
+    """System-2 chunks for prompts of `lens` tokens that reuse `reuse` cached leading tokens each (0: none). Every row of a chunk runs
+    behind ITS prefix in a rectangle of max(lens) - min(reuse) rows, so the engine needs max(reuse) + max(lens) - min(reuse) + tail cache
+    positions (QwenVLEngine.plan; tail = answer + latent queries): rows are ordered by reuse (a look-down turn reuses its whole previous
+    prompt, a fresh call only the template) and a chunk is closed before it would exceed `cap` rows or s_max positions - so the engine
+    never has to drop a row's reuse. Returns lists of indices into lens."""
+    order = sorted(range(len(lens)), key=lambda i: (int(reuse[i]), int(lens[i])))
+    chunks, cur = [], []
+    for i in order:
+        trial = cur + [i]
+        p = [int(reuse[j]) for j in trial]
+        fits = max(p) + max(int(lens[j]) for j in trial) - min(p) + tail <= s_max
+        if cur and (len(cur) >= cap or not fits):
+            chunks.append(cur)
+            cur = [i]
+        else:
+            cur = trial
+    if cur:
+        chunks.append(cur)
+    return chunks
+
+
 class _EnvState:
     def __init__(self, policy: InternVLAN1Net):
         self.policy = policy
@@ -79,7 +101,7 @@ class InternVLAN1Agent:
                 assert processor is not None, "a pre-built model needs its processor"
                 first = InternVLAN1Net(model, processor, num_history=ms.get("num_history", 8), resize_w=ms.get("resize_w", 384),
                                        resize_h=ms.get("resize_h", 384), continuous_traj=ms.get("continuous_traj", True),
-                                       frame_preprocessor=frame_preprocessor)
+                                       frame_preprocessor=frame_preprocessor, kv_reuse=ms.get("kv_reuse", False))
             else:
                 from . import get_config, get_policy
 
@@ -104,6 +126,8 @@ class InternVLAN1Agent:
         self.envs: List[_EnvState] = []
         self.episode_idx = 0
         self.s2_failures = 0     # env-turns that ended in the STOP fallback (visible to the operator; the reference only prints)
+        self.kv_reuse_rows = 0       # kv_reuse: prompt rows taken from the envs' caches instead of being prefilled
+        self.kv_reuse_fallbacks = 0  # kv_reuse: rows whose chunk could not keep their reuse (the engine's rectangle check)
 
     # ------------------------------------------------------------------------------------------------ plugin surface
     def reset(self, reset_index: Optional[List[int]] = None):
@@ -206,11 +230,25 @@ class InternVLAN1Agent:
         # camera-size look-down frame) are right-padded to the longest of the chunk - causal attention makes the padding invisible to
         # the real tokens (QwenVLEngine.prefill seq_lens). Sorted by length so a chunk pads as little as possible.
         built.sort(key=lambda it: it[2]["input_ids"].shape[1])
+        # KV reuse of the policies (kv_reuse): per env the cache of its last System-2 prompt, cropped to where images agree; dropped from
+        # the policy until its new call succeeds (a failing env is reset anyway)
+        past = {}
+        for it in built:
+            pol = it[0].policy
+            if getattr(pol, "kv_reuse", False):
+                past[id(it)], pol._kv = pol.kv_request(it[2]), None
         for items_all in ([built] if built else []):
             model = items_all[0][0].policy.model
             cap = getattr(getattr(model, "qwen", None), "B_max", None) or len(items_all)
             singles = []
-            chunks = [items_all[c0:c0 + cap] for c0 in range(0, len(items_all), cap)]
+            if any(v is not None for v in past.values()):
+                # group by reuse so that mixed chunks (a look-down turn beside a fresh call) keep every row's reuse
+                lens = [int(it[2]["input_ids"].shape[1]) for it in items_all]
+                reuse = [0 if past.get(id(it)) is None else min(past[id(it)].get_seq_length(0), L - 1) for it, L in zip(items_all, lens)]
+                tail = 128 + model.qwen.latent_q.shape[0]
+                chunks = [[items_all[i] for i in c] for c in plan_s2_chunks(lens, reuse, cap, model.qwen.S_max, tail)]
+            else:
+                chunks = [items_all[c0:c0 + cap] for c0 in range(0, len(items_all), cap)]
             while chunks or singles:
                 if not chunks:
                     chunks, singles = singles, []
@@ -232,8 +270,18 @@ class InternVLAN1Agent:
                     gen_extra = dict(extra)
                     if any(kv is not None or want for kv, want in pref):
                         gen_extra.update(prefix_kv=[kv for kv, _ in pref], export_prefix=[want for _, want in pref])
-                    seqs = model.generate(input_ids=ids, pixel_values=pv, image_grid_thw=grid, max_new_tokens=128, do_sample=False,
-                                          use_cache=True, past_key_values=None, return_dict_in_generate=True, **ragged, **gen_extra).sequences
+                    pkv = [past.get(id(it)) for it in items]
+                    res = model.generate(input_ids=ids, pixel_values=pv, image_grid_thw=grid, max_new_tokens=128, do_sample=False, use_cache=True,
+                                         past_key_values=pkv if any(c is not None for c in pkv) else None, return_dict_in_generate=True,
+                                         **ragged, **gen_extra)
+                    seqs = res.sequences
+                    if past:
+                        self.kv_reuse_rows += model.last_kv_reuse["rows"]
+                        self.kv_reuse_fallbacks += model.last_kv_reuse["fallbacks"]
+                        for r, it in enumerate(items):
+                            if getattr(it[0].policy, "kv_reuse", False):
+                                it[0].policy.store_kv(it[2], res.past_key_values.select([r]))
+                    del res
                     if any(want for _, want in pref):
                         kept = model.last_prefix_kv()
                         for r, (it, (_, want)) in enumerate(zip(items, pref)):

@@ -28,10 +28,10 @@ class InternVLAN1AsyncAgent:
         kw = dict(num_history=g("num_history", 8), resize_w=g("resize_w", 384), resize_h=g("resize_h", 384))
         if model is None:
             ms = dict(model_path=g("model_path"), device=str(self.device), env_num=1, device_preprocess=g("device_preprocess", False),
-                      vit_cache=g("vit_cache", False), **kw)
+                      vit_cache=g("vit_cache", False), kv_reuse=g("kv_reuse", False), **kw)
             self.net = InternVLAN1Net(config=InternVLAN1ModelConfig(model_cfg={"model": ms}))
         else:
-            self.net = InternVLAN1Net(model, processor, frame_preprocessor=frame_preprocessor, **kw)
+            self.net = InternVLAN1Net(model, processor, frame_preprocessor=frame_preprocessor, kv_reuse=g("kv_reuse", False), **kw)
         self.model, self.processor = self.net.model, self.net.processor
         self.resize_w, self.resize_h, self.num_history = kw["resize_w"], kw["resize_h"], kw["num_history"]
         self.PLAN_STEP_GAP = g("plan_step_gap", 8)

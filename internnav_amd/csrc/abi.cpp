@@ -170,6 +170,12 @@ int ina_goal_slots(void* Y, int32_t ldy, int32_t y_dtype, int32_t L, int32_t slo
                                  image_w, image_b, pixel_tok, n_pixel, pixel_w, pixel_b, ntok, E, reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_kv_copy(int32_t to_engine, const int64_t* layer_base, int32_t n_layers, const int64_t* seq, int32_t n_seq, int64_t engine_rows,
+                int64_t row_bytes, int64_t max_rows, void* stream) {
+    return ina_launch_kv_copy(to_engine, layer_base, n_layers, seq, n_seq, (long)engine_rows, (long)row_bytes, (long)max_rows,
+                              reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_gemm_select(const ina_gemm_args* args, int* kernel) {
     INA_REQUIRE(args != nullptr && kernel != nullptr, "gemm_select: null argument");
     GemmArgs p;

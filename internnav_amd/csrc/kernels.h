@@ -62,6 +62,8 @@ int ina_launch_goal_slots(void* Y, int ldy, int y_dtype, int L, int slot0, int n
                           const int32_t* row, float* embed, const float* point, int n_point, const float* point_w, const float* point_b,
                           const float* image_tok, int n_image, const float* image_w, const float* image_b, const float* pixel_tok,
                           int n_pixel, const float* pixel_w, const float* pixel_b, int ntok, int E, hipStream_t stream);   // goal_slots.hip
+int ina_launch_kv_copy(int to_engine, const int64_t* layer_base, int n_layers, const int64_t* seq, int n_seq, long engine_rows, long row_bytes,
+                       long max_rows, hipStream_t stream);                                                                   // kv_copy.hip
 int ina_launch_head3(const Head3Args& p, hipStream_t stream);
 int ina_launch_seqpool(const SeqpoolArgs& p, hipStream_t stream);
 int ina_launch_select(const SelectArgs& p, hipStream_t stream);

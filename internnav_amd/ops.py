@@ -330,6 +330,17 @@ def embed3(x: Optional[torch.Tensor], w: Optional[torch.Tensor], bias: Optional[
     return out
 
 
+def kv_copy(layer_base: torch.Tensor, seq: torch.Tensor, engine_rows: int, row_bytes: int, max_rows: int, to_engine: bool) -> None:
+    """row ranges of a KV cache between engine cache slots and caller tensors, every layer and sequence in one launch (bit copy).
+    layer_base: int64 [layers] on the device = address of each layer's cache (engine_rows rows of row_bytes bytes); seq: int64 [n, 4]
+    on the device = (caller address of layer 0's first row, caller layer stride in bytes, first engine row, rows) per sequence.
+    to_engine False: engine -> caller (export), True: caller -> engine (import). The caller checks the caller-side ranges."""
+    assert layer_base.dtype == seq.dtype == torch.int64 and layer_base.is_contiguous() and seq.is_contiguous() and seq.dim() == 2 and seq.shape[1] == 4
+    rc = _lib.lib().ina_kv_copy(int(bool(to_engine)), layer_base.data_ptr(), layer_base.numel(), seq.data_ptr(), seq.shape[0], int(engine_rows),
+                                int(row_bytes), int(max_rows), _stream())
+    _lib.check(rc, "kv_copy")
+
+
 def goal_slots(out: torch.Tensor, L: int, kind: torch.Tensor, row: torch.Tensor, pos: Optional[torch.Tensor] = None, slot0: int = 1,
                nslots: int = 3, embed: Optional[torch.Tensor] = None, point=None, image=None, pixel=None) -> torch.Tensor:
     """goal embedding e of every env b by its kind (0 none: 0, 1 point: w @ point[row[b]] + bias, 2 image / 3 pixel: w @ mean of the

@@ -31,7 +31,7 @@ import torch
 from . import synthetic
 from .navdp import NavDPPolicyDAT
 from .nextdit import NextDiTSystem1
-from .qwen_vl import QwenVLEngine
+from .qwen_vl import ATTN_WIDE_MIN_ROWS, SKINNY_GEMM_MAX_ROWS, EngineKVCache, QwenVLEngine, kv_reuse_fit, kv_reuse_lengths
 from .runtime import CapacityError  # noqa: F401  (re-exported)
 
 
@@ -210,6 +210,9 @@ class InternVLAN1ForCausalLM:
         else:
             self.s1 = NavDPPolicyDAT(_Prefixed(weights, "model.navdp."), s1_cfg or synthetic.N1_NAVDP_CFG, device, max_envs, use_async="async" in system1)
         self._noise_gen = torch.Generator(device=self.device).manual_seed(0)
+        self.kv_reuse_rows = 0          # prompt rows generate(past_key_values=...) took from caches instead of prefilling them (cumulative)
+        self.kv_reuse_fallbacks = 0     # rows that had to run without their cache: the run rectangle would not fit the engine (cumulative)
+        self.last_kv_reuse = dict(rows=0, fallbacks=0)
 
     # ---- construction
     @classmethod
@@ -267,7 +270,13 @@ class InternVLAN1ForCausalLM:
         prompt tokens as an earlier call exported them (the prompt must start with the same P tokens: system prompt + instruction +
         first history frame between the System-2 calls of an episode). Those tokens are not run and their images not encoded;
         pixel_values may still hold every image's patches (the cached images' rows are skipped). Exact: causal attention.
-        export_prefix: one entry per sequence - 0, or the number of leading prompt tokens whose K/V to keep (`last_prefix_kv()`)."""
+        export_prefix: one entry per sequence - 0, or the number of leading prompt tokens whose K/V to keep (`last_prefix_kv()`).
+        past_key_values: an EngineKVCache with one row per sequence, or a list of one-row EngineKVCache / None per sequence, from earlier
+        calls (`return_dict_in_generate=True`). Each sequence takes the K/V of the longest common prefix of its prompt and the cached
+        token ids (cut back to an image boundary and so that the suffix still runs the kernels of a full prefill: exact). The caller vouches
+        that cached images are the same images (only token ids are compared). pixel_values may hold every image or only the others.
+        With return_dict_in_generate and use_cache the result carries `.past_key_values`: an EngineKVCache of every sequence's PROMPT
+        rows (not the answer: see EngineKVCache)."""
         assert not do_sample, "the reference only decodes greedily"
         eos = self.qwen.cfg["eos_token_id"] if eos_token_id is None else eos_token_id
         pv = pixel_values.to(self.device, torch.bfloat16) if pixel_values is not None and pixel_values.numel() else None
@@ -278,7 +287,12 @@ class InternVLAN1ForCausalLM:
             am = attention_mask.cpu().long()
             assert bool((am[:, 1:] <= am[:, :-1]).all()), "ragged System-2 batches are right-padded (mask = 1...1 0...0)"
         pl = 0
-        if prefix_kv is not None and any(k is not None for k in prefix_kv):
+        self.last_kv_reuse = dict(rows=0, fallbacks=0)
+        if past_key_values is not None:
+            assert prefix_kv is None, "past_key_values and prefix_kv are two forms of the same reuse: pass one"
+            pl, pv = self._import_past(input_ids, plens, pv, image_grid_thw, past_key_values, cached_image_embeds,
+                                       max_new_tokens + self.qwen.latent_q.shape[0])
+        elif prefix_kv is not None and any(k is not None for k in prefix_kv):
             assert len(prefix_kv) == B and cached_image_embeds is None, "prefix_kv: one entry per sequence (not combined with cached_image_embeds)"
             pl = np.asarray([0 if k is None else int(k.shape[1]) for k in prefix_kv], dtype=np.int64)
             if int(pl.max()) + S - int(pl.min()) + max_new_tokens + self.qwen.latent_q.shape[0] > self.qwen.S_max:
@@ -329,7 +343,49 @@ class InternVLAN1ForCausalLM:
             seqs[b, :L] = ids_cpu[b, :L]
             seqs[b, L:L + toks.shape[1]] = toks[b]
         seqs = seqs.to(self.device)
-        return SimpleNamespace(sequences=seqs) if return_dict_in_generate else seqs
+        if not return_dict_in_generate:
+            return seqs
+        # a prefill narrower than ATTN_WIDE_MIN_ROWS, or of SKINNY_GEMM_MAX_ROWS rows or fewer, ran other kernels than a full prefill of
+        # a real prompt: only the rows it took from a cache are exact
+        exact = int(state["S_run"]) >= ATTN_WIDE_MIN_ROWS and B * int(state["S_run"]) > SKINNY_GEMM_MAX_ROWS
+        keep = plens if exact else np.broadcast_to(np.asarray(pl, dtype=np.int64), (B,))
+        pkv = self.qwen.kv_handle([ids_cpu[b, : int(keep[b])] for b in range(B)]) if use_cache else None
+        return SimpleNamespace(sequences=seqs, past_key_values=pkv)
+
+    def _import_past(self, input_ids, plens, pv, image_grid_thw, past, cached_image_embeds, tail):
+        """generate(past_key_values=...): reused prompt lengths per sequence, the cached rows put into the batch's cache slots, and
+        pixel_values without the patches of the images inside the reused prefixes."""
+        B = input_ids.shape[0]
+        if isinstance(past, EngineKVCache):
+            assert len(past) == B, f"past_key_values holds {len(past)} rows for a batch of {B}"
+            src = [(past, b) for b in range(B)]
+        else:
+            assert len(past) == B, "past_key_values: one EngineKVCache (or None) per sequence"
+            src = []
+            for c in past:
+                assert c is None or (isinstance(c, EngineKVCache) and len(c) == 1), "past_key_values: one-row EngineKVCache per sequence"
+                src.append(None if c is None else (c, 0))
+        ids = input_ids.cpu().numpy().astype(np.int64)
+        pl = kv_reuse_lengths(ids, plens, [None if s is None else s[0].token_ids[s[1]] for s in src], self.qwen.cfg["image_token_id"])
+        pl, dropped = kv_reuse_fit(pl, ids.shape[1], tail, self.qwen.S_max)
+        self.kv_reuse_fallbacks += dropped
+        self.kv_reuse_rows += int(pl.sum())
+        self.last_kv_reuse = dict(rows=int(pl.sum()), fallbacks=dropped)
+        if not pl.any():
+            return 0, pv
+        self.qwen.import_kv([s if n else None for s, n in zip(src, pl.tolist())], pl)
+        skip = self.qwen.images_in_prefix(input_ids, image_grid_thw, pl)
+        if pv is not None and any(skip):
+            n_rows = [int(t * h * w) for t, h, w in image_grid_thw.tolist()]
+            enc = [True] * len(n_rows) if cached_image_embeds is None else [c is None for c in cached_image_embeds]
+            if pv.shape[0] == sum(r for r, e in zip(n_rows, enc) if e):     # patches of every image to encode: drop the reused ones
+                off = np.concatenate([[0], np.cumsum([r if e else 0 for r, e in zip(n_rows, enc)])])
+                keep = [pv[off[i]:off[i + 1]] for i in range(len(n_rows)) if enc[i] and not skip[i]]
+                pv = torch.cat(keep, 0) if keep else None
+            else:
+                assert pv.shape[0] == sum(r for r, e, k in zip(n_rows, enc, skip) if e and not k), \
+                    "past_key_values: pixel_values must hold the patches of every image to encode, or of those behind the reused prefixes"
+        return pl, pv
 
     def last_prefix_kv(self) -> Dict[int, torch.Tensor]:
         """sequence index of the last generate() call -> the prefix K/V it was asked to export (`export_prefix`)."""
@@ -465,7 +521,7 @@ class InternVLAN1Net:
 
     def __init__(self, config=None, processor=None, num_history: int = 8, resize_w: int = 384, resize_h: int = 384,
                  continuous_traj: bool = True, frame_preprocessor=None, model: Optional[InternVLAN1ForCausalLM] = None,
-                 vit_cache: bool = False, prefix_cache: bool = False):
+                 vit_cache: bool = False, prefix_cache: bool = False, kv_reuse: bool = False):
         """Two ways in, both ending in (model, processor, episode state):
           * the reference's: `InternVLAN1Net(config=InternVLAN1ModelConfig(model_cfg={'model': model_settings}))`
             (internvla_n1_agent.py:39-43, internvla_n1_policy.py:29-48) - loads the checkpoint at model_settings['model_path'] on
@@ -496,8 +552,14 @@ class InternVLAN1Net:
         # chat template, instruction, "These are your historical observations:" and history frame 0 (np.linspace always samples it,
         # internvla_n1_policy.py:125-133); the look-down turn repeats the whole previous prompt. Their K/V of all 28 layers are kept per env
         # (17 MB for 296 tokens) and handed back to generate(): those tokens are not prefilled, frame 0 is not encoded. Exact (causal mask).
+        # KV reuse (model_settings['kv_reuse']): the EngineKVCache of this env's last System-2 call is kept with the identity of every image in
+        # it, and the next call takes the longest prefix on which token ids AND images agree - the whole previous prompt for the look-down
+        # turn, template + instruction + every leading history frame the np.linspace sample repeats otherwise. Works with vit_cache and
+        # supersedes prefix_cache. Exact (causal mask; EngineKVCache / kv_reuse_lengths keep the prefill bit-equal).
+        self.kv_reuse = bool(kv_reuse or (config is not None and dict(config.model_cfg["model"]).get("kv_reuse", False))) \
+            and hasattr(getattr(model, "qwen", None), "kv_handle")
         self.prefix_cache = bool(prefix_cache or (config is not None and dict(config.model_cfg["model"]).get("prefix_cache", False))) \
-            and hasattr(getattr(model, "qwen", None), "export_prefix_kv") and not self.vit_cache
+            and hasattr(getattr(model, "qwen", None), "export_prefix_kv") and not self.vit_cache and not self.kv_reuse
         self.tokenizer = getattr(processor, "tokenizer", None)
         self.num_history, self.resize_w, self.resize_h, self.continuous_traj = num_history, resize_w, resize_h, continuous_traj
         self.device = model.device
@@ -531,7 +593,7 @@ class InternVLAN1Net:
         """a fresh episode state on the same model / processor (the batched agent keeps one per environment)."""
         return InternVLAN1Net(processor=self.processor, num_history=self.num_history, resize_w=self.resize_w, resize_h=self.resize_h,
                               continuous_traj=self.continuous_traj, frame_preprocessor=self.pre, model=self.model, vit_cache=self.vit_cache,
-                              prefix_cache=self.prefix_cache)
+                              prefix_cache=self.prefix_cache, kv_reuse=self.kv_reuse)
 
     def eval(self):
         return self
@@ -545,6 +607,9 @@ class InternVLAN1Net:
         self.input_keys = []          # frame identity of every input image: index into rgb_list, or "look_down"
         self._emb_cache = {}          # frame key -> (embeds bf16 [tokens, H], grid) of the frames of the last System-2 call
         self._prefix = None           # (token ids of the cached prompt prefix, K/V bf16 [layers, P, 1024]) of this episode
+        self.image_keys = []          # identity of every input image: index into rgb_list, or ("look_down", call number) - unique per call
+        self._s2_calls = 0
+        self._kv = None               # (EngineKVCache of the last System-2 prompt, its image_keys) - kv_reuse
 
     def parse_actions(self, output: str) -> List[int]:
         regex = re.compile("|".join(re.escape(a) for a in self.ACTIONS2IDX))
@@ -577,15 +642,18 @@ class InternVLAN1Net:
                 text += f" These are your historical observations: {('<image>' + chr(10)) * len(history_id)}."
             self.input_images = [self.rgb_list[i] for i in sorted(history_id)] + self.rgb_list[-1:]
             self.input_keys = sorted(history_id) + [len(self.rgb_list) - 1]
+            self.image_keys = list(self.input_keys)
             img_id = 0
             self.episode_idx += 1
         else:
             self.input_images.append(image)
             self.input_keys = list(self.input_keys) + ["look_down"]
+            self.image_keys = list(self.image_keys) + [("look_down", self._s2_calls)]
             img_id = -1
             assert self.llm_output != "", "Last llm_output should not be empty when look down"
             text = ""
             self.conversation_history.append({"role": "assistant", "content": [{"type": "text", "text": self.llm_output}]})
+        self._s2_calls += 1
         text += f" {self.CONJUNCTION}<image>."
         content = []
         for part in split_and_clean(text):
@@ -642,6 +710,32 @@ class InternVLAN1Net:
             return self._prefix[1], 0
         return None, P
 
+    def kv_request(self, inputs) -> Optional[EngineKVCache]:
+        """kv_reuse: the last call's cache, cropped to the prefix on which the images agree too (the engine compares token ids only, and
+        every image has the same image-token ids), or None."""
+        if not self.kv_reuse or self._kv is None:
+            return None
+        cache, keys = self._kv
+        ids = inputs["input_ids"][0].cpu()
+        img = self.model.qwen.cfg["image_token_id"]
+        n = min(cache.get_seq_length(0), int(ids.shape[0]))
+        old = cache.token_ids[0][:n]
+        diff = (ids[:n] != old).nonzero()
+        n = int(diff[0]) if diff.numel() else n
+        if n == 0:
+            return None
+        starts = ((ids[:n] == img) & torch.cat([torch.ones(1, dtype=torch.bool), ids[: n - 1] != img])).nonzero().reshape(-1).tolist()
+        for j, st in enumerate(starts):           # the j-th image of both prompts begins at st (the tokens before it are equal)
+            if j >= len(keys) or j >= len(self.image_keys) or keys[j] != self.image_keys[j]:
+                n = st
+                break
+        if n == 0:
+            return None
+        return cache.crop(n)
+
+    def store_kv(self, inputs, cache: Optional[EngineKVCache]):
+        self._kv = None if cache is None or not self.kv_reuse else (cache, list(self.image_keys))
+
     def store_prefix(self, inputs, kv: torch.Tensor):
         self._prefix = (inputs["input_ids"][0, : kv.shape[1]].cpu().clone(), kv)
 
@@ -682,14 +776,26 @@ class InternVLAN1Net:
         kv, want = self.prefix_request(inputs)
         if kv is not None or want:
             extra.update(prefix_kv=[kv], export_prefix=[want])
-        ids = self.model.generate(input_ids=inputs["input_ids"], pixel_values=inputs["pixel_values"], image_grid_thw=inputs["image_grid_thw"],
-                                  max_new_tokens=128, do_sample=False, use_cache=True, past_key_values=None, return_dict_in_generate=True, **extra).sequences
+        past = None
+        if self.kv_reuse:
+            past, self._kv = self.kv_request(inputs), None    # dropped until this call succeeds (S2 failure / retry path)
+            past = [past] if past is not None else None
+        res = self.model.generate(input_ids=inputs["input_ids"], pixel_values=inputs["pixel_values"], image_grid_thw=inputs["image_grid_thw"],
+                                  max_new_tokens=128, do_sample=False, use_cache=True, past_key_values=past, return_dict_in_generate=True, **extra)
+        ids = res.sequences
+        if self.kv_reuse:
+            self.store_kv(inputs, res.past_key_values)
+        del res
         if "cached_image_embeds" in extra:
             self.update_frame_cache(inputs, self.model.last_image_embeds())
         if want:
             self.store_prefix(inputs, self.model.last_prefix_kv()[0])
         extra = {k: v for k, v in extra.items() if k == "cached_image_embeds"}
-        return self.finish_s2(inputs, ids, lambda: self.model.generate_latents(ids, inputs["pixel_values"], inputs["image_grid_thw"], **extra))
+        try:
+            return self.finish_s2(inputs, ids, lambda: self.model.generate_latents(ids, inputs["pixel_values"], inputs["image_grid_thw"], **extra))
+        except Exception:
+            self._kv = None
+            raise
 
     def s1_step_latent(self, rgb, depth, latent) -> S1Output:
         dp_actions = self.model.generate_traj(traj_latents=latent, images_dp=rgb, depths_dp=depth)

@@ -25,6 +25,7 @@ HBM layout (B sequences of S tokens, cache capacity S_max, H = 3584):
 """
 from __future__ import annotations
 
+import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -101,6 +102,135 @@ def rope_index(input_ids: np.ndarray, grids, image_token_id: int, vision_start_i
         pos[:, b] = p
         deltas[b] = int(p.max()) + 1 - S
     return pos, deltas
+
+
+# a GEMM of at most this many rows runs the weight-streaming kernels (csrc/gemm.hip, ina_plan_gemm: kernel 32 for M <= 64), which round
+# differently from the tiled prefill kernels: a prefill stays bit-equal to a longer one only while its run rectangle keeps MORE rows
+SKINNY_GEMM_MAX_ROWS = 64
+# causal attention with fewer than this many query (or key) rows per sequence runs the narrow kernel instead of the wide one that a full
+# prefill of a real prompt runs (csrc/attention_wide.hip, ina_attention_wide_contract): K/V and hidden states then differ in the last bits
+ATTN_WIDE_MIN_ROWS = 128
+
+
+def kv_image_cut(ids: np.ndarray, n: int, image_token_id: int) -> int:
+    """n cut back to the first token of the image it would split (a cached prefix holds whole images or none of an image)."""
+    while 0 < n < ids.shape[0] and ids[n - 1] == image_token_id and ids[n] == image_token_id:
+        n -= 1
+    return n
+
+
+def kv_reuse_lengths(ids: np.ndarray, seq_lens, cached_ids: Sequence[Optional[np.ndarray]], image_token_id: int) -> np.ndarray:
+    """per sequence of a (right-padded) batch ids [B, S]: how many leading prompt tokens to take from a cache holding the K/V of
+    cached_ids[b] (None: nothing cached). The longest common prefix, at least one real token left to run, cut back to the start of an
+    image it would split; then, if the run rectangle (S - min over the batch) would be narrower than ATTN_WIDE_MIN_ROWS or keep
+    SKINNY_GEMM_MAX_ROWS rows or fewer in all, the shortest reuse is cut back until it is not (bit-equality with a full prefill)."""
+    B, S = ids.shape
+    lens = np.asarray(seq_lens, dtype=np.int64).reshape(B)
+    pl = np.zeros(B, dtype=np.int64)
+    for b in range(B):
+        c = cached_ids[b]
+        if c is None or len(c) == 0:
+            continue
+        m = min(len(c), int(lens[b]) - 1)
+        diff = np.nonzero(ids[b, :m] != np.asarray(c[:m]))[0]
+        n = int(diff[0]) if diff.size else m
+        pl[b] = kv_image_cut(ids[b], n, image_token_id)
+    need = max(ATTN_WIDE_MIN_ROWS, SKINNY_GEMM_MAX_ROWS // B + 1)   # rectangle width of the kernels a full prefill runs
+    if pl.any() and S - int(pl.min()) < need:
+        b = int(np.argmin(pl))
+        pl[b] = kv_image_cut(ids[b], max(0, min(int(pl[b]), S - need)), image_token_id)
+    return pl
+
+
+def kv_reuse_fit(pl: np.ndarray, S: int, tail: int, s_max: int) -> Tuple[np.ndarray, int]:
+    """drop the reuse of the rows with the longest prefixes until the run rectangle (every row's suffix starts behind ITS prefix, plus the
+    answer and the latent queries: tail) fits a cache of s_max positions -> (prefix lengths, number of rows dropped)."""
+    pl = np.asarray(pl, dtype=np.int64).copy()
+    dropped = 0
+    while pl.any() and int(pl.max()) + S - int(pl.min()) + tail > s_max:
+        pl[int(np.argmax(pl))] = 0
+        dropped += 1
+    return pl, dropped
+
+
+class EngineKVCache:
+    """K/V of the PROMPT rows of each sequence of a System-2 call, per row bf16 [layers, n_b, kv_w] with the token ids (int64, CPU) they
+    cover: what `generate(return_dict_in_generate=True, use_cache=True).past_key_values` returns and `generate(past_key_values=...)`
+    takes back. The subset of HF's `Cache` its callers use: get_seq_length, crop, row selection, copy.deepcopy.
+    Unlike HF's cache it does not hold the decoded answer: the decode passes run the weight-streaming GEMMs, which round differently
+    from the tiled prefill, so the next call prefills the answer with the rest of its new tokens (a handful of rows).
+    A fresh handle is a VIEW of the engine's cache slots (no copy). It is materialised into tensors of its own - one ina_kv_copy launch for
+    every live handle concerned - when deepcopy / materialize() is called, or just before the engine would overwrite its rows."""
+
+    def __init__(self, token_ids: Sequence[Optional[torch.Tensor]], kv: Optional[Sequence[Optional[torch.Tensor]]] = None, engine=None,
+                 views: Optional[Sequence[Optional[Tuple[int, int]]]] = None):
+        n = len(token_ids)
+        self.token_ids = [None if t is None else torch.as_tensor(t).detach().to("cpu", torch.int64).reshape(-1) for t in token_ids]
+        self.kv = list(kv) if kv is not None else [None] * n
+        self._views = list(views) if views is not None else [None] * n     # per row: (slot, generation) while the rows live in a cache slot
+        assert len(self.kv) == len(self._views) == n
+        for b in range(n):
+            if self.get_seq_length(b) == 0:
+                self.kv[b], self._views[b] = None, None
+            else:
+                assert (self.kv[b] is None) != (self._views[b] is None), "a row is either a view of a cache slot or holds its own K/V"
+                assert self.kv[b] is None or self.kv[b].shape[1] == self.get_seq_length(b)
+        self._engine = engine if any(v is not None for v in self._views) else None
+        if self._engine is not None:
+            self._engine._kv_views.add(self)
+
+    def __len__(self) -> int:
+        return len(self.token_ids)
+
+    @property
+    def batch_size(self) -> int:
+        return len(self.token_ids)
+
+    def get_seq_length(self, row: int = 0) -> int:
+        t = self.token_ids[row]
+        return 0 if t is None else int(t.numel())
+
+    @property
+    def is_view(self) -> bool:
+        return any(v is not None for v in self._views)
+
+    def crop(self, max_length: int) -> "EngineKVCache":
+        """keep the first max_length tokens of every row (HF: a negative value removes that many from the end)."""
+        for b in range(len(self)):
+            n = self.get_seq_length(b)
+            m = n + max_length if max_length < 0 else max_length
+            if n == 0 or n <= m:
+                continue
+            m = max(m, 0)
+            self.token_ids[b] = self.token_ids[b][:m]
+            if self.kv[b] is not None:
+                self.kv[b] = self.kv[b][:, :m]
+            if m == 0:
+                self.token_ids[b], self.kv[b], self._views[b] = None, None, None
+        return self
+
+    def select(self, rows: Sequence[int]) -> "EngineKVCache":
+        """a handle over the given rows (views stay views of the same slots; tensors are shared, never written in place)."""
+        rows = [int(r) for r in rows]
+        return EngineKVCache([self.token_ids[r] for r in rows], [self.kv[r] for r in rows], self._engine, [self._views[r] for r in rows])
+
+    def batch_select_indices(self, indices) -> None:
+        """HF name: keep the given rows, in place."""
+        o = self.select(torch.as_tensor(indices).reshape(-1).tolist())
+        self.token_ids, self.kv, self._views = o.token_ids, o.kv, o._views
+        if self._engine is not None and self.is_view:
+            self._engine._kv_views.add(self)
+
+    def materialize(self) -> "EngineKVCache":
+        if self._engine is not None and self.is_view:
+            self._engine.materialize_kv([(self, b) for b in range(len(self)) if self._views[b] is not None])
+        return self
+
+    def __deepcopy__(self, memo):
+        kv = [None if t is None else t.clone() for t in self.kv]
+        c = EngineKVCache([None if t is None else t.clone() for t in self.token_ids], kv, self._engine, list(self._views))
+        c.materialize()                                          # straight from the cache slots: this handle stays a view
+        return c
 
 
 def _interleave16(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -216,6 +346,12 @@ class QwenVLEngine:
         axis = np.concatenate([np.full(16, 0), np.full(24, 1), np.full(24, 2)]).astype(np.int32)  # mrope_section [16, 24, 24]
         assert axis.size == half
         self.axis_of = torch.from_numpy(axis).to(dev)
+        self._kv_reset_tracking()
+
+    def _kv_reset_tracking(self):
+        self._kv_views = weakref.WeakSet()                       # live EngineKVCache handles with rows still in this engine's cache slots
+        self._slot_gen = np.zeros(self.B_max, dtype=np.int64)    # bumped when a slot is rewritten from row 0: views of older generations are gone
+        self._kv_base = None                                     # int64 [layers] device table of the layers' cache addresses (ina_kv_copy)
 
     _BUFFERS = ("pv_perm", "xv", "hv", "attv", "qkvv", "ffv", "mh", "emb", "emb_tok", "v_cos", "v_sin", "x_in", "x", "h", "att", "qkv", "ff", "cos", "sin",
                 "hl", "xl", "logits", "next_tok")
@@ -231,6 +367,7 @@ class QwenVLEngine:
             setattr(t, n, torch.empty_like(getattr(self, n)))
         t.layers = [dict(L, kv=torch.empty_like(L["kv"])) for L in self.layers]
         t._side = None
+        t._kv_reset_tracking()
         return t
 
     # ------------------------------------------------------------------------------------------------ vision tower
@@ -315,6 +452,7 @@ class QwenVLEngine:
             ph["k_len"] = torch.from_numpy(np.asarray(k_len, dtype=np.int32)).to(dev)
         # the new tokens of every sequence are its LAST S keys (what the attention launch assumes when it appends them itself, ina_attn_args.rope_cos)
         ph["new_are_last"] = bool(np.all((np.asarray(k_len).reshape(-1) if k_len is not None else ph["Lk"]) == pos0[:, 0] + S))
+        ph["w0"] = pos0[:, 0].copy()                              # first cache row each sequence writes (live KV handles, _kv_evict)
         return ph
 
     def _layers(self, ph: dict):
@@ -322,6 +460,8 @@ class QwenVLEngine:
         H, nh, nkv, hd, Smax = self.H, self.nh, self.nkv, self.hd, self.S_max
         B, S = ph["B"], ph["S"]
         rows, r0, b0 = B * S, ph.get("r0", 0), ph.get("b0", 0)
+        if self._kv_views and "w0" in ph:
+            self._kv_evict({b0 + i: int(w) for i, w in enumerate(ph["w0"])})
         x, h, att, qkv, ff, x_in, cos, sin = (t[r0:r0 + rows] for t in (self.x, self.h, self.att, self.qkv, self.ff, self.x_in, self.cos, self.sin))
         ops.mrope_table(ph["pos"], self.inv_freq, self.axis_of, cos, sin)
         q4 = qkv[:, : nh * hd].view(B, S, nh, hd)
@@ -336,7 +476,7 @@ class QwenVLEngine:
             vn4 = qkv[:, (nh + nkv) * hd:].view(B, S, nkv, hd)
         for li, L in enumerate(self.layers):
             src = x_in if li == 0 else x
-            wf = (lambda k, L=L: L.get(k)) if (self.frag_weights and rows > 64) else (lambda k: None)
+            wf = (lambda k, L=L: L.get(k)) if (self.frag_weights and rows > SKINNY_GEMM_MAX_ROWS) else (lambda k: None)
             if fused_norm:
                 ops.linear(src, L["qkv_w"], bias=L["qkv_b"], out=qkv, prenorm=(L["n1"], 1e-6))
             else:
@@ -493,6 +633,8 @@ class QwenVLEngine:
         return P
 
     def run_prefill(self, P: dict, pixel_values: Optional[torch.Tensor]):
+        if self._kv_views:                                        # live KV handles on rows this prefill writes: ONE export launch for all
+            self._kv_evict({b: int(w) for b, w in enumerate(P["prefill"]["w0"])})
         ops.gather_rows(self.embed, self.x_in, src=P["ids"])
         if self.split_prefill and P.get("split") and self.tap is None:
             if "traj_src" in P:
@@ -601,6 +743,8 @@ class QwenVLEngine:
         """kv bf16 [m, layers, n, kv_w]: the prefixes of m environments into batch slots 0 .. m-1 (one strided copy per layer)."""
         m, nl, n, w = kv.shape
         assert nl == len(self.layers) and w == self.kv_w and m <= self.B_max and n <= self.S_max and kv.dtype == torch.bfloat16
+        if self._kv_views:
+            self._kv_evict({b: 0 for b in range(m)})
         for li, L in enumerate(self.layers):
             L["kv"].view(self.B_max, self.S_max, self.kv_w)[:m, :n].copy_(kv[:, li])
 
@@ -608,8 +752,86 @@ class QwenVLEngine:
         """put an exported prefix back into batch slot `seq` (before plan(..., prefix_len=kv.shape[1]) / prefill(..., prefix_len=))."""
         n = kv.shape[1]
         assert kv.shape == (len(self.layers), n, self.kv_w) and kv.dtype == torch.bfloat16 and n <= self.S_max
+        if self._kv_views:
+            self._kv_evict({seq: 0})
         for li, L in enumerate(self.layers):
             L["kv"].view(self.B_max, self.S_max, self.kv_w)[seq, :n].copy_(kv[li])
+
+    # ---- KV handles (EngineKVCache): views of cache slots, materialised / imported with ina_kv_copy (one launch per direction)
+    def kv_handle(self, token_ids: Sequence[Optional[torch.Tensor]]) -> EngineKVCache:
+        """a handle over the first len(token_ids[b]) cached rows of slots 0 .. B-1 (a view: nothing is copied now)."""
+        return EngineKVCache(token_ids, None, self, [(b, int(self._slot_gen[b])) for b in range(len(token_ids))])
+
+    def _kv_copy(self, entries, to_engine: bool):
+        """entries: (tensor bf16 [layers, n, kv_w] with contiguous rows, slot, n) -> one ina_kv_copy launch over all of them."""
+        if not entries:
+            return
+        nl, w = len(self.layers), self.kv_w
+        if self._kv_base is None:
+            self._kv_base = torch.tensor([L["kv"].data_ptr() for L in self.layers], dtype=torch.int64, device=self.device)
+        tab = np.zeros((len(entries), 4), dtype=np.int64)
+        for i, (t, slot, n) in enumerate(entries):
+            assert t.dtype == torch.bfloat16 and t.device == self.device and t.dim() == 3 and t.shape[0] == nl and t.shape[2] == w
+            assert t.stride(2) == 1 and t.stride(1) == w and 0 < n <= t.shape[1] and 0 <= slot < self.B_max and n <= self.S_max
+            assert t.data_ptr() % 16 == 0 and (t.stride(0) * 2) % 16 == 0, "ina_kv_copy moves 16-byte units"
+            tab[i] = (t.data_ptr(), t.stride(0) * 2, slot * self.S_max, n)
+        ops.kv_copy(self._kv_base, torch.from_numpy(tab).to(self.device), self.B_max * self.S_max, w * 2, int(tab[:, 3].max()), to_engine)
+
+    def materialize_kv(self, rows):
+        """rows: (handle, row) pairs that are views of this engine's slots -> each gets K/V tensors of its own (one export launch)."""
+        entries, todo = [], []
+        for h, b in rows:
+            v = h._views[b]
+            if v is None or any(h is h2 and b == b2 for h2, b2 in todo):
+                continue
+            slot, gen = v
+            if gen != self._slot_gen[slot]:
+                raise RuntimeError(f"EngineKVCache row {b}: cache slot {slot} was rewritten before the handle was materialised")
+            n = h.get_seq_length(b)
+            t = torch.empty(len(self.layers), n, self.kv_w, dtype=torch.bfloat16, device=self.device)
+            entries.append((t, slot, n))
+            todo.append((h, b))
+        self._kv_copy(entries, to_engine=False)
+        for (h, b), (t, _, _) in zip(todo, entries):
+            h.kv[b], h._views[b] = t, None
+        for h, _ in todo:
+            if not h.is_view:
+                self._kv_views.discard(h)
+                h._engine = None
+
+    def _kv_evict(self, writes: Dict[int, int], extra=()):
+        """before rows [writes[slot], ...) of the given slots are written: materialise every live view that covers one of them (plus the
+        (handle, row) pairs in `extra`), all in one export launch; a slot written from row 0 starts a new generation."""
+        rows = list(extra)
+        for h in list(self._kv_views):
+            for b, v in enumerate(h._views):
+                if v is not None and v[0] in writes and h.get_seq_length(b) > writes[v[0]] and v[1] == self._slot_gen[v[0]]:
+                    rows.append((h, b))
+        self.materialize_kv(rows)
+        for slot, w in writes.items():
+            if w == 0:
+                self._slot_gen[slot] += 1
+
+    def import_kv(self, sources, prefix_len: np.ndarray):
+        """sources[b]: (EngineKVCache, row) or None; prefix_len[b] leading rows of each source go into cache slot b. A source that is
+        still a view of slot b itself is already in place; every other one is materialised if need be (one export launch, together
+        with the live views these writes would clobber) and copied in (one import launch)."""
+        writes, need = {}, []
+        for b, src in enumerate(sources):
+            n = int(prefix_len[b])
+            if src is None or n == 0:
+                writes[b] = 0
+                continue
+            h, r = src
+            v = h._views[r]
+            in_place = v is not None and h._engine is self and v[0] == b and v[1] == self._slot_gen[b]
+            writes[b] = n if in_place else 0
+            if not in_place:
+                need.append((h, r, b, n))
+        self._kv_evict(writes, extra=[(h, r) for h, r, _, _ in need if h._engine is self])
+        for h, r, _, _ in need:
+            assert h.kv[r] is not None, "past_key_values of another engine: materialize() it first"
+        self._kv_copy([(h.kv[r], b, n) for h, r, b, n in need], to_engine=True)
 
     # ---- eager, stateful API (used by the policy layer: answers have data-dependent lengths)
     def prefill(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor], image_grid_thw, cached_embeds: Optional[list] = None,
