@@ -34,6 +34,13 @@ __device__ __forceinline__ float ina_gelu_tanh(float x) {
 }
 __device__ __forceinline__ float ina_silu(float x) { return x / (1.0f + __expf(-x)); }
 
+// w . x of one nn.Linear(3, C) output in one fixed order of explicit fused multiply-adds. embed3 and goal_slots both use it, so a point goal
+// gets the same bits from either kernel: under -ffp-contract=fast the plain expression was fused differently per template instance and per
+// unrolled loop copy (goal_slots' point slots differed from embed3's fp32 output in the last bit).
+__device__ __forceinline__ float ina_dot3(float w0, float w1, float w2, float x0, float x1, float x2) {
+    return __builtin_fmaf(w2, x2, __builtin_fmaf(w0, x0, w1 * x1));
+}
+
 __device__ __forceinline__ float ina_act(float v, int act) {
     switch (act) {
         case INA_ACT_GELU_ERF: return ina_gelu_erf(v);

@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void embed3_kernel(Embed3Args p, int vec) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float a = 0.f;
-            if (p.X) a = w[3 * j] * x0 + w[3 * j + 1] * x1 + w[3 * j + 2] * x2;
+            if (p.X) a = ina_dot3(w[3 * j], w[3 * j + 1], w[3 * j + 2], x0, x1, x2);
             if (p.b) a += bb[j];
             if (p.P) a += pp[j];
             v[j] = a;

@@ -43,8 +43,8 @@ __global__ __launch_bounds__(256) void goal_slots_kernel(GoalSlotsArgs p) {
     } else if (k == 1) {
         const float* x = p.point + (size_t)r * 3;
         const float x0 = x[0], x1 = x[1], x2 = x[2];
-        for (int d = tid; d < p.D; d += 256) {      // the expression of embed3, so a point env gets the bits of the point-goal call
-            float a = p.point_w[d * 3] * x0 + p.point_w[d * 3 + 1] * x1 + p.point_w[d * 3 + 2] * x2;
+        for (int d = tid; d < p.D; d += 256) {      // the arithmetic of embed3, so a point env gets the bits of the point-goal call
+            float a = ina_dot3(p.point_w[d * 3], p.point_w[d * 3 + 1], p.point_w[d * 3 + 2], x0, x1, x2);
             a += p.point_b[d];
             emb[d] = a;
         }
