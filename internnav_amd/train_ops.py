@@ -114,7 +114,8 @@ def colsum_chunks(group_rows: int) -> int:
 
 
 def colsum(x, x2=None, out=None, group_rows=0, accumulate=False, scale=1.0, x2_bcast=False, out_cs=1, x_bcast=False):
-    """out[g, c] (+)= scale * sum_{rows of group g} x[r, c] * x2[r, c];  x2_bcast: x2 is [rows] (one value per row)."""
+    """out[g, c] (+)= scale * sum_{rows of group g} x[r, c] * x2[r, c];  x2_bcast: x2 is [rows] (one value per row); x_bcast: x is [rows] and x2
+    [rows, C] carries the columns; scale = 0 is read as the default 1."""
     rows = x.shape[0]
     a = _lib.ColsumArgs()
     if x_bcast:
@@ -239,7 +240,8 @@ def small_linear(x, w, bias=None, tab=None, out=None, out_dtype=torch.float32, w
 
 def mse_masked(pred, target, mask, T: int, loss_scale: float = 1.0, want_grad: bool = True):
     """masked MSE of internvla_n1.py:283-286: pred [nseq*T, >=D] (row stride free), target f32 [nseq*T, D], mask f32 [nseq].
-    Returns (loss f32 [1], dpred f32 [nseq*T, D] or None)."""
+    Returns (loss f32 [1], dpred f32 [nseq*T, D] or None). A batch whose mask sums to 0 (every sequence masked) gives loss = 0 and dpred = 0,
+    where the reference expression divides by zero: such a micro-batch contributes nothing to the step."""
     pred = _2d(pred)
     assert target.dtype == torch.float32 and target.is_contiguous() and mask.dtype == torch.float32 and mask.is_contiguous()
     rows, D = target.shape

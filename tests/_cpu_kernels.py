@@ -1,8 +1,9 @@
 """TEST INFRASTRUCTURE: torch (CPU) stand-ins for the kernel wrappers of `internnav_amd.ops` / `internnav_amd.train_ops`, with the same
 call contracts (dtypes, strides, in-place outputs, accumulate flags). They let the CPU test run exercise the WIRING of the SFT tape
 (`internnav_amd/sft.py`: which op feeds which, what every backward closure accumulates where) against the oracle's autograd without a GPU.
-They are never imported by the product package; the kernels themselves are tested on the GPU against the same formulas
-(tests/test_train_ops_gpu.py) and the whole step against the oracle (tests/test_sft_gpu.py)."""
+They are never imported by the product package. Stand-in and kernel are tied together through tests/train_ops_ref.py: the same argument sets
+(tests/train_ops_cases.py) run through the stand-ins on the CPU (tests/test_train_ops_ref_cpu.py) and through the kernels on the GPU
+(tests/test_train_kernels_fp64_gpu.py), both against the float64 reference; the whole step is checked against the oracle (tests/test_sft_gpu.py)."""
 from __future__ import annotations
 
 import math
@@ -96,7 +97,7 @@ def affine(x, scale=None, s_div=1, s_f=None, base=None, tab=None, out=None, out_
         y = y + base.float()
     if tab is not None:
         t = tab.reshape(-1, y.shape[1])
-        y = y + t.repeat(y.shape[0] // t.shape[0], 1)
+        y = y + t[torch.arange(y.shape[0]) % t.shape[0]]                       # the kernel's rule: tab[r % len(tab)], any length
     return _store(out, y, out_dtype or x.dtype, accumulate)
 
 
@@ -120,12 +121,12 @@ def glu_bwd(a, b, dy, da=None, db=None):
     return _store(da, ga, a.dtype), _store(db, gb, b.dtype)
 
 
-def colsum(x, x2=None, out=None, group_rows=0, accumulate=False, scale=1.0, x2_bcast=False, out_cs=1, **_):
-    v = x.float()
+def colsum(x, x2=None, out=None, group_rows=0, accumulate=False, scale=1.0, x2_bcast=False, out_cs=1, x_bcast=False):
+    v = x.float().reshape(-1, 1) if x_bcast else x.float()                     # x_bcast: x is one value per row, x2 carries the columns
     if x2 is not None:
         v = v * (x2.float().reshape(-1, 1) if x2_bcast else x2.float())
     gr = group_rows or v.shape[0]
-    s = v.view(v.shape[0] // gr, gr, v.shape[1]).sum(1) * scale
+    s = v.view(v.shape[0] // gr, gr, v.shape[1]).sum(1) * (scale if scale != 0 else 1.0)      # the library reads scale 0 as "default 1"
     if out is None:
         return s
     s = s.reshape(out.shape)                      # 1-D bias / strided weight-column views, [G, C] tables, [1, n] flattened tables
@@ -178,7 +179,7 @@ def small_linear(x, w, bias=None, tab=None, out=None, out_dtype=F32, w_transpose
         y = y + bias
     if tab is not None:
         t = tab.reshape(-1, y.shape[1])
-        y = y + t.repeat(y.shape[0] // t.shape[0], 1)
+        y = y + t[torch.arange(y.shape[0]) % t.shape[0]]
     return _store(out, y, out_dtype)
 
 
@@ -187,8 +188,9 @@ def mse_masked(pred, target, mask, T, loss_scale=1.0, want_grad=True):
     m = mask.repeat_interleave(T)[:, None]
     e = pred.float()[:, :D] - target
     denom = mask.sum() * T * D
-    loss = ((m * e * e).sum() / denom).view(1)
-    return loss, (2.0 * m * e / denom * loss_scale if want_grad else None)
+    inv = 1.0 / denom if denom > 0 else torch.zeros(())                        # an all-masked batch: loss 0, dpred 0 (the kernel's contract)
+    loss = ((m * e * e).sum() * inv).view(1)
+    return loss, (2.0 * m * e * inv * loss_scale if want_grad else None)
 
 
 def dropout(x, p, seed, out=None, out_dtype=None, salt=None):
@@ -208,13 +210,18 @@ def sumsq_parts(flat, width=1024):
 
 
 def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step, p_bf16=None, sumsq_parts=None, max_norm=0.0, grad_scale=1.0, norm_out=None, zero_grad=False):
+    # the hyper-parameters reach the kernel as fp32 values and 1 - beta is formed from those (1 - fp32(0.999) is 1.3e-5 below 0.001), while the
+    # bias corrections are computed by the wrapper in double precision: the same here
+    f = lambda t: float(torch.tensor(t, dtype=F32))
+    bc1, bc2 = f(1 - beta1 ** step), f(1 - beta2 ** step)
+    lr, beta1, beta2, eps, wd, grad_scale, max_norm = f(lr), f(beta1), f(beta2), f(eps), f(wd), f(grad_scale), f(max_norm)
     total = float(sumsq_parts.sum().sqrt()) * grad_scale if sumsq_parts is not None else 0.0
     clip = min(1.0, max_norm / (total + 1e-6)) if max_norm > 0 else 1.0
     gg = g * (grad_scale * clip)
     p.mul_(1 - lr * wd)
     m.mul_(beta1).add_(gg, alpha=1 - beta1)
     v.mul_(beta2).addcmul_(gg, gg, value=1 - beta2)
-    p.addcdiv_(m, v.sqrt() / math.sqrt(1 - beta2 ** step) + eps, value=-lr / (1 - beta1 ** step))
+    p.addcdiv_(m, v.sqrt() / math.sqrt(bc2) + eps, value=-lr / bc1)
     if p_bf16 is not None:
         p_bf16.copy_(p)
     if norm_out is not None:
