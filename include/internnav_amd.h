@@ -349,7 +349,8 @@ typedef struct ina_mrope_table_args {
 } ina_mrope_table_args;
 int ina_mrope_table(const ina_mrope_table_args* args, void* stream);
 
-/* ---- argmax_rows: out[r] = argmax_j X[r, j] (first maximum), greedy decoding (HF generate do_sample=False) */
+/* ---- argmax_rows: out[r] = argmax_j X[r, j] (first maximum), greedy decoding (HF generate do_sample=False).
+ *      NaN entries are never selected; a row with no entry above -inf (all -inf or all NaN) returns 0. The result is always in [0, n). */
 typedef struct ina_argmax_args {
     const float* X;         /* f32 [rows, ldx] */
     int32_t* out;           /* int32 [rows] */

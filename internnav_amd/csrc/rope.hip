@@ -90,7 +90,9 @@ __global__ __launch_bounds__(256) void mrope_table_kernel(MropeTableArgs p) {
     }
 }
 
-// 1024 threads per row, 16-byte loads: the row (152064 logits = 594 KiB) is a single latency-bound stream for one workgroup
+// 1024 threads per row, 16-byte loads: the row (152064 logits = 594 KiB) is a single latency-bound stream for one workgroup.
+// NaN entries never compare greater and are never selected; a row without any entry above -inf (all -inf, all NaN) gives 0, as torch.argmax
+// does for all -inf: the result indexes the embedding table of the next launch and is always in [0, n).
 __global__ __launch_bounds__(1024) void argmax_kernel(ArgmaxArgs p) {
     __shared__ float bv[16];
     __shared__ int bi[16];
@@ -120,7 +122,7 @@ __global__ __launch_bounds__(1024) void argmax_kernel(ArgmaxArgs p) {
     if (threadIdx.x == 0) {
         for (int w = 1; w < 16; ++w)
             if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-        p.out[r] = idx;
+        p.out[r] = best > -INFINITY ? idx : 0;   // no entry above -inf: idx is the start value or whichever -inf a scalar tail met
     }
 }
 
