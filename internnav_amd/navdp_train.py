@@ -8,7 +8,7 @@ of the 16-layer pre-LN decoder (ng / mg causal; the two critic passes over the l
 the ng condition hidden), the action / critic / aux heads and the weighted MSE sum; then adamw_torch (lr 1e-4, cosine to 0, no warmup,
 clip 1.0, weight decay 0 unless set - with HF's no-decay group for LayerNorm parameters and biases).
 
-This module is that step on the define-by-run tape of `sft.py` (the kernels of libinternnav_amd.so; torch for allocation, views, index
+This module is that step on the define-by-run tape of `tape.py` and the layers of `train_layers.py` (the kernels of libinternnav_amd.so; torch for allocation, views, index
 tables and RNG draws only). The passes that share weights are batched: ng and mg are 2B causal sequences of one decoder run, the two critic
 passes 2B sequences of another, whose memory is the ng condition from row 4 on (the reference's -inf memory mask on slots 0..3) tiled twice.
 
@@ -25,8 +25,9 @@ from typing import Dict, Iterable, List, Optional
 import torch
 
 from . import train_ops as T
-from .sft import (BF, F32, RESNET_MEAN, RESNET_STD, DinoTrain, ParamStore, Tape, Var, _acc, ddpm_alphas_cumprod, decoder_layer,
-                  decoder_layer_prenorm, sinusoidal_pos_emb)
+from .tape import F32, ParamStore, Tape, Var
+from .train_layers import (RESNET_MEAN, RESNET_STD, DinoTrain, ddpm_add_noise, ddpm_alphas_cumprod, decoder_layer_prenorm, rgbd_former,
+                           sinusoidal_pos_emb)
 from .synthetic import NAVDPNET_CFG
 
 IDENTITY = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
@@ -74,34 +75,6 @@ def cosine_lr(lr: float, step: int, total_steps: Optional[int]) -> float:
 
 
 # ---------------------------------------------------------------------------------------------------------------- tape helpers
-def _rows(tape: Tape, x: Var, r0: int, r1: int) -> Var:
-    """row slice view; its gradient lands in the matching rows of x's gradient."""
-    y = Var(x.v[r0:r1], req=x.req)
-
-    def bwd():
-        if y.g is None or not x.req:
-            return
-        if x.g is None or not x.own or x.g.dtype != F32:
-            full = torch.zeros(x.v.shape, dtype=F32, device=x.v.device)
-            if x.g is not None:
-                T.affine(x.g, out=full)
-            x.g, x.own = full, True
-        T.affine(y.g, out=x.g[r0:r1], accumulate=True)
-    tape.nodes.append(bwd)
-    return y
-
-
-def _tile(tape: Tape, x: Var, times: int) -> Var:
-    """[rows, C] -> [times * rows, C] (the same block `times` over); gradient = the sum of the blocks."""
-    y = Var(x.v.repeat(times, 1), req=x.req)
-
-    def bwd():
-        if y.g is not None:
-            _acc(x, y.g.float().view(times, *x.v.shape).sum(0))
-    tape.nodes.append(bwd)
-    return y
-
-
 def _critic_memory(tape: Tape, cond: Var, B: int, Lc: int, first: int) -> Var:
     """rows first..Lc-1 of the B ng condition sequences (the first B*Lc rows of cond), tiled for the label and the augment pass:
     [2B * (Lc - first), C]. The reference's memory mask (-inf on slots 0..first-1, navdp_policy.py:130-131) as a K/V view."""
@@ -115,22 +88,9 @@ def _critic_memory(tape: Tape, cond: Var, B: int, Lc: int, first: int) -> Var:
             return
         g = torch.zeros(cond.v.shape, dtype=F32, device=cond.v.device)
         g[: B * Lc].view(B, Lc, Cd)[:, first:] = y.g.float().view(2, B, Lm, Cd).sum(0)
-        _acc(cond, g)
+        tape.accumulate(cond, g)
     tape.nodes.append(bwd)
     return y
-
-
-def _small_linear_bwd(P, name: str, x: torch.Tensor, dy: torch.Tensor, in_features: int):
-    """weight / bias gradient of a small_linear(x [rows, in_features], W [N, in_features]) from dy f32 [rows, N] (in_features = 3: the
-    point goal / action inputs; the heads pass their token width)."""
-    gw = P.grad(name + ".weight")
-    if in_features <= 3:
-        for kk in range(in_features):
-            T.colsum(dy, x[:, kk], out=gw[:, kk], x2_bcast=True, out_cs=in_features, accumulate=True)
-    else:
-        for n in range(dy.shape[1]):
-            T.colsum(x, dy[:, n], out=gw[n], x2_bcast=True, accumulate=True)
-    T.colsum(dy, out=P.grad(name + ".bias"), accumulate=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the loss
@@ -166,15 +126,6 @@ class NavDPNetTrainHead:
         tok = dino.forward(tape, img.to(device=self.device, dtype=F32).contiguous())
         return tape.linear(tape.mean_tokens(tok, dino.L), p + "project_layer.weight", p + "project_layer.bias", out_dtype=F32)
 
-    def _aux(self, goal: Var, name: str, pg: torch.Tensor, ones: torch.Tensor, scale: float):
-        """aux head Linear(D, 3) on a goal embedding + its `scale`-weighted MSE against the point goal; returns the unweighted MSE."""
-        P = self.P
-        out = T.small_linear(goal.v, P.w32(name + ".weight"), P.w32(name + ".bias"))
-        mse, dout = T.mse_masked(out, pg, ones, 1, loss_scale=scale)
-        _small_linear_bwd(P, name, goal.v, dout, goal.v.shape[1])
-        _acc(goal, T.small_linear(dout, P.w32(name + ".weight"), w_transposed=True))
-        return mse
-
     def loss_and_grads(self, batch: Dict[str, torch.Tensor], draws: Dict[str, torch.Tensor], seed: int = 0,
                        loss_scale: float = 1.0) -> Dict[str, torch.Tensor]:
         """batch: the navdp_collate_fn dict; draws: ng_noise / mg_noise f32 [B, T, 3], ng_t / mg_t int [B] (the two sample_noise draws).
@@ -192,29 +143,15 @@ class NavDPNetTrainHead:
         # ---- rgbd_encoder (navdp_backbone.py:248-286): frozen RGB tokens, trainable depth tokens, former_net, project_layer
         rgb = self.rgb.forward(tape, batch["batch_rgb"].to(dev).reshape(B * M, *batch["batch_rgb"].shape[2:]))
         dep = self.depth.forward(tape, batch["batch_depth"].to(device=dev, dtype=F32).reshape(B, 224, 224, 1))
-        tok = tape.add_table(tape.cat_tokens([(rgb, M * 256), (dep, 256)], B), "rgbd_encoder.former_pe.position_embedding.weight", Lf)
-        fq = Var(P.w32("rgbd_encoder.former_query.position_embedding.weight").unsqueeze(0).expand(B, -1, -1).reshape(B * Lm, 384))
+        rgbd = rgbd_former(tape, tape.cat_tokens([(rgb, M * 256), (dep, 256)], B), B, Lf, Lm, "former_pe.position_embedding.weight",
+                           "former_query.position_embedding.weight")                                            # bf16 [B*Lm, D]
 
-        def bwd_fq():
-            if fq.g is not None:
-                P.grad("rgbd_encoder.former_query.position_embedding.weight").add_(fq.g.float().view(B, -1).sum(0).view(Lm, 384))
-        tape.nodes.append(bwd_fq)
-        q = fq
-        for i in range(2):
-            q = decoder_layer(tape, q, tok, f"rgbd_encoder.former_net.layers.{i}", B, Lm, Lf, 8, 384)
-        rgbd = tape.linear(q, "rgbd_encoder.project_layer.weight", "rgbd_encoder.project_layer.bias")            # bf16 [B*Lm, D]
-
-        # ---- goal embeddings and aux heads
-        point = Var(T.small_linear(pg, P.w32("point_encoder.weight"), P.w32("point_encoder.bias")))              # f32 [B, D]
-
-        def bwd_point():
-            if point.g is not None:
-                _small_linear_bwd(P, "point_encoder", pg, point.g.float().contiguous(), 3)
-        tape.nodes.append(bwd_point)
+        # ---- goal embeddings and aux heads (Linear(D, 3) on a goal embedding, 0.25-weighted MSE against the point goal)
+        point = tape.small_linear(pg, "point_encoder")                                                           # f32 [B, D]
         image = self._goal(tape, self.image, batch["batch_ig"], "image_encoder.")
         pixel = self._goal(tape, self.pixel, batch["batch_tg"], "pixel_encoder.")
-        l_img = self._aux(image, "image_aux_head", pg, ones, 0.25 * loss_scale)
-        l_pix = self._aux(pixel, "pixel_aux_head", pg, ones, 0.25 * loss_scale)
+        l_img, = tape.mse_head(image, "image_aux_head", pg, ones, 1, 0.25 * loss_scale)
+        l_pix, = tape.mse_head(pixel, "pixel_aux_head", pg, ones, 1, 0.25 * loss_scale)
 
         # ---- conditions of the 2B noise passes [ng b = 0..B-1 | mg b = 0..B-1]: [time, 3 goal slots, rgbd] + cond_pos_embed, self.drop
         gi = (goal_slot_table(B) * B + torch.arange(B)[:, None]).reshape(-1).to(dev)                            # rows of [point; image; pixel]
@@ -231,17 +168,16 @@ class NavDPNetTrainHead:
             g = torch.zeros(3 * B, D, dtype=F32, device=dev)
             g.index_add_(0, gi, hd.g.float().view(2 * B, 4, D)[B:, 1:].reshape(3 * B, D))
             for i, var in enumerate((point, image, pixel)):
-                _acc(var, g[i * B:(i + 1) * B].clone())
+                tape.accumulate(var, g[i * B:(i + 1) * B].clone())
         tape.nodes.append(bwd_goals)
-        cond = tape.cat_tokens([(hd, 4), (_tile(tape, rgbd, 2), Lm)], 2 * B)
+        cond = tape.cat_tokens([(hd, 4), (tape.repeat_seq(rgbd, 1, B * Lm, 2), Lm)], 2 * B)         # the rgbd block once per noise pass
         cond = tape.dropout(tape.add_table(cond, "cond_pos_embed.position_embedding.weight", Lc))                  # f32 [2B*Lc, D]
 
         # ---- action embeddings [ng | mg | label | augment] (label / augment: input_embed detached), + out_pos_embed, self.drop
         lab = labels.reshape(B, Tn, 3)
         aug = batch["batch_augments"].to(device=dev, dtype=F32).reshape(B, Tn, 3)
         noise = torch.cat([draws["ng_noise"], draws["mg_noise"]]).to(device=dev, dtype=F32).reshape(2 * B, Tn, 3)
-        a = self.acp[ts].view(2 * B, 1, 1)
-        noisy = a.sqrt() * lab.repeat(2, 1, 1) + (1 - a).sqrt() * noise                                          # DDPM add_noise
+        noisy = ddpm_add_noise(self.acp, ts, lab.repeat(2, 1, 1), noise)
         acts = torch.cat([noisy, lab, aug]).reshape(4 * B * Tn, 3).contiguous()
         tab = P.w32("out_pos_embed.position_embedding.weight")[:Tn].contiguous()
         x = Var(T.small_linear(acts, P.w32("input_embed.weight"), P.w32("input_embed.bias"), tab=tab))         # f32 [4B*Tn, D]
@@ -252,14 +188,14 @@ class NavDPNetTrainHead:
                 return
             dy = dy.float().contiguous()
             n = 2 * B * Tn
-            _small_linear_bwd(P, "input_embed", acts[:n], dy[:n], 3)
+            tape.small_linear_grad("input_embed", acts[:n], dy[:n])                  # the label / augment rows are detached
             T.colsum(dy.view(4 * B, Tn * D), out=P.grad("out_pos_embed.position_embedding.weight").view(-1, D)[:Tn].view(1, -1), accumulate=True)
         tape.nodes.append(bwd_embed)
         x = tape.dropout(x)
 
         # ---- the 16-layer decoder: 2B causal noise sequences, 2B critic sequences over the ng condition rows 4..
-        y = _rows(tape, x, 0, 2 * B * Tn)
-        z = _rows(tape, x, 2 * B * Tn, 4 * B * Tn)
+        y = tape.rows(x, 0, 2 * B * Tn)
+        z = tape.rows(x, 2 * B * Tn, 4 * B * Tn)
         mem_cr = _critic_memory(tape, cond, B, Lc, 4)
         for i in range(cfg["temporal_depth"]):
             y = decoder_layer_prenorm(tape, y, cond, f"decoder.layers.{i}", 2 * B, Tn, Lc, H, D, causal=True)
@@ -268,24 +204,12 @@ class NavDPNetTrainHead:
 
         # ---- heads and losses (navdp_trainer.py:80-101)
         pred = tape.norm(y, "layernorm.weight", "layernorm.bias", 1e-5)                                        # bf16 [2B*Tn, D]
-        out = T.small_linear(pred.v, P.w32("action_head.weight"), P.w32("action_head.bias"))                   # f32 [2B*Tn, 3]
-        target = noise.reshape(2 * B * Tn, 3)
-        n = B * Tn
-        l_ng, d_ng = T.mse_masked(out[:n], target[:n].contiguous(), ones, Tn, loss_scale=0.4 * loss_scale)
-        l_mg, d_mg = T.mse_masked(out[n:], target[n:].contiguous(), ones, Tn, loss_scale=0.4 * loss_scale)
-        dout = torch.cat([d_ng, d_mg])
-        _small_linear_bwd(P, "action_head", pred.v, dout, D)
-        pred.g = T.small_linear(dout, P.w32("action_head.weight"), out_dtype=BF, w_transposed=True)
+        l_ng, l_mg = tape.mse_head(pred, "action_head", noise.reshape(2 * B * Tn, 3), ones, Tn, 0.4 * loss_scale, blocks=2)
 
         pc = tape.norm(z, "layernorm.weight", "layernorm.bias", 1e-5, out_dtype=F32)
         pooled = tape.mean_tokens(pc, Tn)                                                                       # f32 [2B, D]
-        cr = T.small_linear(pooled.v, P.w32("critic_head.weight"), P.w32("critic_head.bias"))                 # f32 [2B, 1]
         ct = torch.cat([batch["batch_label_critic"], batch["batch_augment_critic"]]).to(device=dev, dtype=F32).view(2 * B, 1)
-        l_cl, d_cl = T.mse_masked(cr[:B], ct[:B].contiguous(), ones, 1, loss_scale=0.2 * loss_scale)
-        l_ca, d_ca = T.mse_masked(cr[B:], ct[B:].contiguous(), ones, 1, loss_scale=0.2 * loss_scale)
-        dcr = torch.cat([d_cl, d_ca])
-        _small_linear_bwd(P, "critic_head", pooled.v, dcr, D)
-        pooled.g = T.small_linear(dcr, P.w32("critic_head.weight"), w_transposed=True)
+        l_cl, l_ca = tape.mse_head(pooled, "critic_head", ct, ones, 1, 0.2 * loss_scale, blocks=2)                 # label | augment
 
         self.last_dropout_sites = dict(tape.sites)
         tape.backward()
@@ -340,16 +264,8 @@ class NavDPNetTrainer:
     def optimizer_step(self) -> torch.Tensor:
         """clip_grad_norm_(max_grad_norm) over all trainable tensors + torch.optim.AdamW with the decay / no-decay groups, one global norm;
         gradients are zeroed. Returns the pre-clip gradient norm (f32 [1] device tensor)."""
-        P = self.P
-        lr = self.current_lr()
-        P.step_count += 1
-        parts = T.sumsq_parts(P.g32) if self.max_grad_norm > 0 else None
-        cut = self.head.decay_end
-        for lo, hi, wd in ((0, cut, self.weight_decay), (cut, P.numel, 0.0)):
-            if hi > lo:
-                T.adamw(P.p32[lo:hi], P.g32[lo:hi], P.m[lo:hi], P.v[lo:hi], lr, self.betas[0], self.betas[1], self.eps, wd, P.step_count,
-                        p_bf16=P.p16[lo:hi], sumsq_parts=parts, max_norm=self.max_grad_norm, norm_out=self.norm, zero_grad=True)
-        P.version += 1
+        self.P.adamw_step(self.current_lr(), self.betas, self.eps, self.weight_decay, self.max_grad_norm, norm_out=self.norm,
+                          decay_end=self.head.decay_end)
         self.step_idx += 1
         return self.norm
 

@@ -6,7 +6,7 @@ the N_QUERY `<traj>` tokens appended behind each sample's own tokens (`t_s_pos[b
 `image_grid_thw` of the Qwen processor, `traj_images` [B, T, 224, 224, 3], `traj_poses` [B, T, 32, 3], `video_frame_num` [B].
 
 Step = frozen System-2 forward of the tokens before `t_s_pos` (ViT + LLM prefill, ragged batch, KV cache kept)  ->  latent-query rows
-(`sft_llm.LatentQueryGrad`)  ->  System-1 loss and gradients (`sft.NextDiTSftHead`)  ->  latent-query backward  ->  gradient reduction
+(`sft_llm.LatentQueryGrad`)  ->  System-1 loss and gradients (`sft.NextDiTSftHead`, on the tape of `tape.py`)  ->  latent-query backward  ->  gradient reduction
 over the data-parallel ranks (ONE flat bucket; all-reduce, or reduce-scatter + sharded update + all-gather = ZeRO-2)  ->  fused
 clip + AdamW. Optimiser / schedule: adamw_torch, lr 1e-4 -> cosine_with_min_lr 1e-5, warm-up ratio 0.003, weight decay 0, clip 1.0
 (train_dual_system.sh:72-77).
@@ -19,7 +19,6 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import train_ops as T
 from .qwen_vl import QwenVLEngine
 from .sft import NavDPSftHead, NextDiTSftHead
 from .sft_llm import LatentQueryGrad
@@ -383,25 +382,12 @@ class InternVLAN1SftTrainer:
     def optimizer_step(self) -> float:
         lr = cosine_with_min_lr(self.step_idx, self.total_steps, self.warmup_steps, self.lr, self.min_lr)
         P = self.P
+        # ZeRO-2: this rank's shard only, the global gradient norm from the shards' partial sums
+        P.adamw_step(lr, self.betas, self.eps, self.wd, self.max_norm, grad_scale=1.0 / self.world, norm_out=self.grad_norm,
+                     reduce_parts=lambda parts: torch.distributed.all_reduce(parts, group=self.pg))
         if self.world > 1 and self.zero2:
-            lo, hi = shard_bounds(P.numel, self.world, self.rank)
-            parts = T.sumsq_parts(P.g32[lo:hi]) if hi > lo else torch.zeros(1024, dtype=torch.float32, device=self.device)
-            torch.distributed.all_reduce(parts, group=self.pg)          # global gradient norm from the shards' partial sums
-            P.step_count += 1
-            if hi > lo:
-                T.adamw(P.p32[lo:hi], P.g32[lo:hi], P.m, P.v, lr, self.betas[0], self.betas[1], self.eps, self.wd, P.step_count,
-                        p_bf16=P.p16[lo:hi], sumsq_parts=parts, max_norm=self.max_norm, grad_scale=1.0 / self.world, norm_out=self.grad_norm)
-            P.g32.zero_()
-            per = shard_bounds(P.numel, self.world, 0)[1]
             for buf in (P.p32, P.p16):                                  # all-gather the updated master / working weights
-                full = torch.empty(per * self.world, dtype=buf.dtype, device=self.device)
-                mine = torch.zeros(per, dtype=buf.dtype, device=self.device)
-                mine[: hi - lo].copy_(buf[lo:hi])
-                torch.distributed.all_gather_into_tensor(full, mine, group=self.pg)
-                buf.copy_(full[: P.numel])
-            P.version += 1
-        else:
-            P.adamw_step(lr, self.betas, self.eps, self.wd, self.max_norm, grad_scale=1.0 / self.world, norm_out=self.grad_norm)
+                buf.copy_(self._gather_flat(buf[P.m_lo:P.m_hi]))
         self.engine.latent_q.copy_(P.w16(LQ).view(self.engine.latent_q.shape))
         self.step_idx += 1
         return lr
@@ -416,7 +402,7 @@ class InternVLAN1SftTrainer:
         return {(prefix + k if k == LQ else p1 + k): v for k, v in self.P.state_dict().items()}
 
     def _gather_flat(self, shard: torch.Tensor) -> torch.Tensor:
-        """all-gather of a ZeRO-2 shard into the full flat buffer (padded like the p32 / p16 all-gather of optimizer_step)."""
+        """all-gather of a ZeRO-2 shard into the full flat buffer (padded to equal shards; optimizer_step gathers p32 / p16 with it, checkpoint() the moments)."""
         per = shard_bounds(self.P.numel, self.world, 0)[1]
         mine = torch.zeros(per, dtype=shard.dtype, device=self.device)
         mine[: shard.numel()].copy_(shard)

@@ -30,7 +30,7 @@ KPAD = 592  # 3*14*14 = 588 padded to a multiple of 8
 
 
 def patch_kpad(channels: int) -> int:
-    """im2col row width of a patch-embed conv weight [384, channels, 14, 14] (the rule of sft.DinoTrain): max(C, 3)*196 rounded up to a
+    """im2col row width of a patch-embed conv weight [384, channels, 14, 14] (the rule of train_layers.DinoTrain): max(C, 3)*196 rounded up to a
     multiple of 8 - a 1-channel input is replicated to 3 channels."""
     return (max(channels, 3) * PATCH * PATCH + 7) // 8 * 8
 

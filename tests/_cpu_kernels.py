@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE: torch (CPU) stand-ins for the kernel wrappers of `internnav_amd.ops` / `internnav_amd.train_ops`, with the same
 call contracts (dtypes, strides, in-place outputs, accumulate flags). They let the CPU test run exercise the WIRING of the SFT tape
-(`internnav_amd/sft.py`: which op feeds which, what every backward closure accumulates where) against the oracle's autograd without a GPU.
+(`internnav_amd/tape.py` and the heads built on it in `sft.py` / `navdp_train.py`: which op feeds which, what every backward closure accumulates where) against the oracle's autograd without a GPU.
 They are never imported by the product package. Stand-in and kernel are tied together through tests/train_ops_ref.py: the same argument sets
 (tests/train_ops_cases.py) run through the stand-ins on the CPU (tests/test_train_ops_ref_cpu.py) and through the kernels on the GPU
 (tests/test_train_kernels_fp64_gpu.py), both against the float64 reference; the whole step is checked against the oracle (tests/test_sft_gpu.py)."""

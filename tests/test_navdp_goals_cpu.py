@@ -121,7 +121,7 @@ def test_partial_goal_tower_is_refused():
 
 @pytest.mark.parametrize("cin", [1, 3, 4, 6, 7])
 def test_patch_embed_width_follows_the_conv_weight(cin):
-    """K = max(C, 3) * 196 padded to a multiple of 8 (sft.DinoTrain's rule); C = 3 keeps the padded weight it had (592 columns, 4 zeros)."""
+    """K = max(C, 3) * 196 padded to a multiple of 8 (train_layers.DinoTrain's rule); C = 3 keeps the padded weight it had (592 columns, 4 zeros)."""
     spec = S.dinov2_vits_spec("")
     spec["patch_embed.proj.weight"] = ((384, cin, 14, 14), "w")
     sd = S.materialize(spec, seed=2)

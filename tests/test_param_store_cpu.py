@@ -3,7 +3,7 @@ import torch
 
 
 def test_flat_store_layout_and_views():
-    from internnav_amd.sft import ParamStore
+    from internnav_amd.tape import ParamStore
 
     g = torch.Generator().manual_seed(0)
     tensors = {"a.weight": torch.randn(384, 3, generator=g), "a.bias": torch.randn(384, generator=g), "conv": torch.randn(8, 3, 14, 14, generator=g),
@@ -32,7 +32,7 @@ def test_flat_store_layout_and_views():
 
 
 def test_frozen_store_has_no_optimizer_state():
-    from internnav_amd.sft import ParamStore, _Params
+    from internnav_amd.tape import ParamStore, _Params
 
     t = {"rgb_model.w": torch.ones(16, 8)}
     F = ParamStore(t, "cpu", trainable=False)
@@ -48,7 +48,7 @@ def test_checkpoint_resume_roundtrip(tmp_path):
     engine's latent queries follow, and a mismatching trainable set is refused."""
     import pytest
 
-    from internnav_amd.sft import ParamStore
+    from internnav_amd.tape import ParamStore
     from internnav_amd.trainer import LQ, InternVLAN1SftTrainer
 
     def make(seed):

@@ -67,7 +67,7 @@ def _sft_worker(rank, world, port, q, backend="nccl"):
 
     dev = _device(rank, backend)
     dist.init_process_group(backend, **({"device_id": dev} if backend == "nccl" else {"rank": rank, "world_size": world}))
-    from internnav_amd.sft import ParamStore
+    from internnav_amd.tape import ParamStore
     from internnav_amd.trainer import InternVLAN1SftTrainer, shard_bounds
 
     if backend != "nccl":            # CPU twin: torch stand-ins for the two HIP kernels of the optimiser (the collectives are under test)

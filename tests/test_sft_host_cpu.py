@@ -9,7 +9,7 @@ from oracle.schedulers import DDPMScheduler
 
 
 def test_sinusoidal_tables_and_ddpm_schedule():
-    from internnav_amd import sft as E
+    from internnav_amd import train_layers as E
 
     t = torch.tensor([1.0, 37.0, 999.0, 1000.0])
     assert torch.equal(E.timestep_embedding(t), o_nd.timestep_embedding(t))
@@ -31,7 +31,7 @@ def _dense(idx, coef, n_src):
 
 def test_pos_embed_resampling_as_sparse_rows():
     """DinoTrain builds the 37x37 -> 16x16 bicubic resampling (dinov2.py:180-211) as a sparse row mix and its transpose for the gradient."""
-    from internnav_amd.sft import DinoTrain
+    from internnav_amd.train_layers import DinoTrain
 
     d = DinoTrain("rgb_model.", "cpu")
     g = torch.Generator().manual_seed(0)

@@ -98,7 +98,7 @@ def _zero2_worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from internnav_amd import train_ops as T
-    from internnav_amd.sft import ParamStore
+    from internnav_amd.tape import ParamStore
     from internnav_amd.trainer import InternVLAN1SftTrainer, shard_bounds
 
     T.adamw = _cpu_adamw                                                     # the GPU kernels are not under test here: the collectives are
@@ -166,7 +166,7 @@ def _zero2_ckpt_worker(rank, world, port, q, tmp):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from internnav_amd import train_ops as T
-    from internnav_amd.sft import ParamStore
+    from internnav_amd.tape import ParamStore
     from internnav_amd.trainer import InternVLAN1SftTrainer, shard_bounds
 
     T.adamw = _cpu_adamw
