@@ -255,6 +255,20 @@ int ina_goal_slots(void* Y, int32_t ldy, int32_t y_dtype, int32_t L, int32_t slo
 int ina_kv_copy(int32_t to_engine, const int64_t* layer_base, int32_t n_layers, const int64_t* seq, int32_t n_seq, int64_t engine_rows,
                 int64_t row_bytes, int64_t max_rows, void* stream);
 
+/* ---- memory_gather: the visual-memory rows of the NavDPNet former's token buffer for n stepped envs of a rollout, from a per-env ring of
+ *      cached frame tokens, in ONE launch (graph capturable; reference memory semantics: navdp_lerobot_dataset.py:215-222).
+ *  ring  f32 [max_envs, depth, ntok, C]: final-LayerNorm tokens of each env's last depth = (M - 1) * stride + 1 frames, without positions;
+ *  fresh f32 [n, ntok, C]: the tokens of this step's new frame of launch row i; blank f32 [ntok, C]: the tokens of an all-zero frame;
+ *  pe    f32 [M * ntok, C]: the former's positional table; env / head / count: device int32 [n] = the env of launch row i, the ring slot its
+ *  new frame goes to, and its pushes since the last reset (this one included).
+ *  ring[env[i], head[i]] = fresh[i];  out[i * out_env_stride + (j * ntok + p) * C ...] (bf16, contiguous rows) = bf16(src + pe[j * ntok + p]) with
+ *  src = fresh[i] for j = M - 1, ring[env[i], (head[i] - (M-1-j) * stride) mod depth] when (M-1-j) * stride < count[i], else blank.
+ *  The env ids of one launch are distinct (caller's contract); an entry outside the ring yields NaN rows, never an out-of-bounds access.
+ *  16-byte aligned tensors, C a multiple of 8. Plain arguments: no struct, no ABI bump. */
+int ina_memory_gather(void* out, int64_t out_env_stride, float* ring, const float* fresh, const float* blank, const float* pe, const int32_t* env,
+                      const int32_t* head, const int32_t* count, int32_t n, int32_t max_envs, int32_t M, int32_t ntok, int32_t C, int32_t depth,
+                      int32_t stride, void* stream);
+
 /* ---- head3: final norm + Linear(C, 3) + sampler update, one wave per row.
  *      e = W . (norm(X[r]) * gamma + beta) * (1 + mod_scale[r / mod_div]) ... + b
  *      mode 0: eps_out[r] = e ; mode 1 (DDPM, diffusers DDPMScheduler.step): x0 = clamp((s - c1 e) c0, +-clip),

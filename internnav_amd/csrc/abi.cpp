@@ -176,6 +176,13 @@ int ina_kv_copy(int32_t to_engine, const int64_t* layer_base, int32_t n_layers, 
                               reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_memory_gather(void* out, int64_t out_env_stride, float* ring, const float* fresh, const float* blank, const float* pe, const int32_t* env,
+                      const int32_t* head, const int32_t* count, int32_t n, int32_t max_envs, int32_t M, int32_t ntok, int32_t C, int32_t depth,
+                      int32_t stride, void* stream) {
+    return ina_launch_memory_gather(out, (long)out_env_stride, ring, fresh, blank, pe, env, head, count, n, max_envs, M, ntok, C, depth, stride,
+                                    reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_gemm_select(const ina_gemm_args* args, int* kernel) {
     INA_REQUIRE(args != nullptr && kernel != nullptr, "gemm_select: null argument");
     GemmArgs p;

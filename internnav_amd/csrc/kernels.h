@@ -64,6 +64,9 @@ int ina_launch_goal_slots(void* Y, int ldy, int y_dtype, int L, int slot0, int n
                           int n_pixel, const float* pixel_w, const float* pixel_b, int ntok, int E, hipStream_t stream);   // goal_slots.hip
 int ina_launch_kv_copy(int to_engine, const int64_t* layer_base, int n_layers, const int64_t* seq, int n_seq, long engine_rows, long row_bytes,
                        long max_rows, hipStream_t stream);                                                                   // kv_copy.hip
+int ina_launch_memory_gather(void* out, long out_env_stride, float* ring, const float* fresh, const float* blank, const float* pe,
+                             const int32_t* env, const int32_t* head, const int32_t* count, int n, int max_envs, int M, int ntok, int C, int depth,
+                             int stride, hipStream_t stream);                                                                // memory_gather.hip
 int ina_launch_head3(const Head3Args& p, hipStream_t stream);
 int ina_launch_seqpool(const SeqpoolArgs& p, hipStream_t stream);
 int ina_launch_select(const SelectArgs& p, hipStream_t stream);

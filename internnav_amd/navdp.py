@@ -393,11 +393,19 @@ class NavDPNet(_NavDPBase):
 
     def encode_rgbd(self, B: int, images: torch.Tensor, depths: torch.Tensor):
         """RGBDBackbone.forward (navdp_backbone.py:248-286): tokens -> cond rows 4.. (+ cond_pos_embed[4:])."""
-        M, Lc, D = self.M, self.Lc, self.D
+        M = self.M
         nt = (M + 1) * 256
         tok = self.former.tokens[: B * nt]
         self.rgb.forward(images.reshape(B * M, 224, 224, 3), self.vit_ws, tok, out_map=(M * 256, nt, 0),
                          pos=self.former.pe[: M * 256], mean=IMAGENET_MEAN, std=IMAGENET_STD)
+        self.encode_depth_and_former(B, depths)
+
+    def encode_depth_and_former(self, B: int, depths: torch.Tensor):
+        """the RGB rows of the former's token buffer are filled (by encode_rgbd, or from a rollout session's token ring): the depth tower
+        into the last 256 rows of every env, then former_net + project_layer -> cond rows 4.. (+ cond_pos_embed[4:])."""
+        M, Lc, D = self.M, self.Lc, self.D
+        nt = (M + 1) * 256
+        tok = self.former.tokens[: B * nt]
         self.depth_vit.forward(depths.reshape(B, 224, 224, 1), self.vit_ws, tok, out_map=(256, nt, M * 256),
                                pos=self.former.pe[M * 256:])
         cond3 = self.cond[: B * Lc].view(B, Lc, D)
@@ -469,12 +477,7 @@ class NavDPNet(_NavDPBase):
         goal_point is [B,3] or [n_point,3] (see goal_plan). Each goal tower runs once over its sub-batch, ina_goal_slots fills the goal
         slots of every env in one launch, and the RGB-D encoder, the sampler, the critic and the ranking run once over all B envs.
         -> (negative, positive) f32 [B,8,T,3]; the goal embeddings stay in self.goal_embed[:B]."""
-        kinds = torch.as_tensor(goal_kind)
-        for code, kind in ((GOAL_IMAGE, "image"), (GOAL_PIXEL, "pixel")):
-            if kind not in self.goal_towers and bool((kinds == code).any()):
-                miss = self.missing_goal_keys[kind]
-                raise KeyError(f"this NavDPNet checkpoint has no {kind}-goal encoder: {len(miss)} parameters are missing, e.g. {miss[:4]}")
-        plan = goal_plan(kinds, goal_point, goal_image, goal_pixel, pixel_channel=self.pixel_channel)
+        plan = self._plan_goals(goal_kind, goal_point, goal_image, goal_pixel)
         B = plan.B
         if not (B <= self.b_max and input_images.shape[0] == B and x_init.shape[0] == B and step_noise.shape[1] == B):
             raise ValueError(f"{B} goal kinds, {input_images.shape[0]} image stacks, {x_init.shape[0]} x_init rows, "
@@ -484,6 +487,15 @@ class NavDPNet(_NavDPBase):
         self.encode_rgbd(B, input_images, input_depths)
         self.encode_goals(plan, plan_dev, goal_point, goal_image, goal_pixel)
         return self._sample_and_rank(B, x_init, step_noise)
+
+    def _plan_goals(self, goal_kind, goal_point, goal_image, goal_pixel) -> GoalPlan:
+        """goal_plan of a mixed-goal batch, after refusing a goal kind whose encoder this checkpoint lacks."""
+        kinds = torch.as_tensor(goal_kind)
+        for code, kind in ((GOAL_IMAGE, "image"), (GOAL_PIXEL, "pixel")):
+            if kind not in self.goal_towers and bool((kinds == code).any()):
+                miss = self.missing_goal_keys[kind]
+                raise KeyError(f"this NavDPNet checkpoint has no {kind}-goal encoder: {len(miss)} parameters are missing, e.g. {miss[:4]}")
+        return goal_plan(kinds, goal_point, goal_image, goal_pixel, pixel_channel=self.pixel_channel)
 
     def encode_goals(self, plan: GoalPlan, plan_dev: torch.Tensor, goal_point, goal_image, goal_pixel):
         """goal towers over their compact sub-batches (fp32 tokens into self.goal_tok), then cond rows 1..3 of every env (+ cond_pos_embed)

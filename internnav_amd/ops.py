@@ -341,6 +341,29 @@ def kv_copy(layer_base: torch.Tensor, seq: torch.Tensor, engine_rows: int, row_b
     _lib.check(rc, "kv_copy")
 
 
+def memory_gather(out: torch.Tensor, ring: torch.Tensor, fresh: torch.Tensor, blank: torch.Tensor, pe: torch.Tensor, env: torch.Tensor,
+                  head: torch.Tensor, count: torch.Tensor, stride: int = 1) -> torch.Tensor:
+    """visual-memory token rows of n stepped envs from the per-env ring of cached frame tokens, and the new frame into the ring (one launch).
+    out bf16 [n, rows_per_env >= M * ntok, C] (contiguous rows): out[i, j * ntok + p] = bf16(src + pe[j * ntok + p]); ring f32 [max_envs, depth,
+    ntok, C] with depth = (M - 1) * stride + 1; fresh f32 [n, ntok, C]; blank f32 [ntok, C]; pe f32 [M * ntok, C]; env / head / count int32 [n]
+    on the device (include/internnav_amd.h: ina_memory_gather). The env ids of one launch must be distinct."""
+    n, ntok, Cd = fresh.shape
+    max_envs, depth = ring.shape[0], ring.shape[1]
+    M = pe.shape[0] // ntok
+    assert out.dtype == torch.bfloat16 and out.dim() == 3 and out.shape[0] == n and out.shape[2] == Cd and out.stride(2) == 1 and out.stride(1) == Cd
+    assert out.shape[1] >= M * ntok and (n == 1 or out.stride(0) >= M * ntok * Cd)
+    for t in (ring, fresh, blank, pe):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert ring.shape == (max_envs, depth, ntok, Cd) and blank.shape == (ntok, Cd) and pe.shape == (M * ntok, Cd) and depth == (M - 1) * stride + 1
+    for t in (env, head, count):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n and t.device == out.device
+    rc = _lib.lib().ina_memory_gather(out.data_ptr(), out.stride(0) if n > 1 else max(out.stride(0), M * ntok * Cd), ring.data_ptr(),
+                                      fresh.data_ptr(), blank.data_ptr(), pe.data_ptr(), env.data_ptr(), head.data_ptr(), count.data_ptr(), n,
+                                      max_envs, M, ntok, Cd, depth, stride, _stream())
+    _lib.check(rc, "memory_gather")
+    return out
+
+
 def goal_slots(out: torch.Tensor, L: int, kind: torch.Tensor, row: torch.Tensor, pos: Optional[torch.Tensor] = None, slot0: int = 1,
                nslots: int = 3, embed: Optional[torch.Tensor] = None, point=None, image=None, pixel=None) -> torch.Tensor:
     """goal embedding e of every env b by its kind (0 none: 0, 1 point: w @ point[row[b]] + bias, 2 image / 3 pixel: w @ mean of the
