@@ -269,6 +269,21 @@ int ina_memory_gather(void* out, int64_t out_env_stride, float* ring, const floa
                       const int32_t* head, const int32_t* count, int32_t n, int32_t max_envs, int32_t M, int32_t ntok, int32_t C, int32_t depth,
                       int32_t stride, void* stream);
 
+/* ---- traj_actions: the step's action table from the sampled System-1 trajectories of B envs, in ONE launch (graph capturable, no host
+ *      synchronisation) - what vln_utils.traj_to_actions computes on the host per env (vln_utils.py:63-136), rounding for rounding.
+ *  traj  f32|bf16 (traj_dtype: INA_F32 | INA_BF16) [B, S, T, 3], the S samples of an env contiguous (generate_traj's [S * B, T, 3]); x, y are
+ *        x4-scaled increments. Per env: x, y * 0.25; sequential fp32 running sum over t per sample; fp64 mean over the S samples in sample order
+ *        with a leading zero row -> the mean trajectory [T + 1, 2]; greedy pure pursuit in fp64 (0.25 m steps, 15 degree turns, look-ahead 4, stop
+ *        radius 0.2 m): 1 forward, 2 left, 3 right.
+ *  actions int32 [B, max_actions] = the first max_actions entries of the host's list, zero-padded; count int32 [B] = min(len(list), max_actions).
+ *        1 <= max_actions <= 256; the loop ends once max_actions entries exist (the policy path uses 4).
+ *  traj_out f64 [B, T + 1, 2] or NULL: receives the mean trajectory (bit-equal to the host's numpy result).
+ *  scale_in_place != 0: x * 0.25, y * 0.25 are written back into traj, the reference's in-place un-normalisation (vln_utils.py:129).
+ *  S >= 1, 1 <= T <= 1023. atan2 / cos / sin differ from the host libm by a few ulp: a decision whose margin is below that may fall the other
+ *  way (margins of real trajectories are >= 1e-5; tests/traj_actions_ref.py). Plain arguments: no struct, no ABI bump. */
+int ina_traj_actions(void* traj, int32_t traj_dtype, int32_t B, int32_t S, int32_t T, int32_t* actions, int32_t max_actions, int32_t* count,
+                     double* traj_out, int32_t scale_in_place, void* stream);
+
 /* ---- head3: final norm + Linear(C, 3) + sampler update, one wave per row.
  *      e = W . (norm(X[r]) * gamma + beta) * (1 + mod_scale[r / mod_div]) ... + b
  *      mode 0: eps_out[r] = e ; mode 1 (DDPM, diffusers DDPMScheduler.step): x0 = clamp((s - c1 e) c0, +-clip),

@@ -291,6 +291,7 @@ SYMBOLS = {
     "ina_kv_copy": (C.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p]),
     "ina_memory_gather": (C.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                     c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "ina_traj_actions": (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "ina_head3": (C.c_int, [C.POINTER(Head3Args), c_void_p]),
     "ina_seqpool_head": (C.c_int, [C.POINTER(SeqpoolArgs), c_void_p]),
     "ina_select_traj": (C.c_int, [C.POINTER(SelectArgs), c_void_p]),

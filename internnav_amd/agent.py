@@ -86,7 +86,9 @@ class InternVLAN1Agent:
         `policy = get_policy(policy_name)(config=get_config(policy_name)(model_cfg={'model': model_settings}))`, which loads the
         checkpoint at model_settings['model_path'] on model_settings['device'] and the HF processor from the same path.
         model_settings read: model_path, device, policy_name, infer_mode ('sync' | 'partial_async'), sys2_max_forward_step, num_history,
-        resize_w/h, width/height (camera), continuous_traj, env_num (engine capacity), device_preprocess (optional).
+        resize_w/h, width/height (camera), continuous_traj, env_num (engine capacity), device_preprocess (optional), device_actions
+        (optional, default False: System-1's trajectories become the step's action table in one kernel launch instead of one numpy
+        traj_to_actions per env; `last_action_table` then holds the int32 [n, 4] table of the last System-1 call on the device).
         Tests / bench may pass a built `model` + `processor`, or a `policy_factory() -> InternVLAN1Net`, instead."""
         self.config = config
         ms = getattr(config, "model_settings", None) or (config.get("model_settings") if isinstance(config, dict) else {}) or {}
@@ -95,6 +97,9 @@ class InternVLAN1Agent:
         self.sys1_depth_threshold = 5.0
         self.sys1_forward_step = 4
         self._ms = ms
+        self.device_actions = bool(ms.get("device_actions", False))
+        self.last_action_table: Optional[torch.Tensor] = None    # device_actions: int32 [n, 4], row k = the k-th env of the last step that ran System-1
+        self._tables: List[torch.Tensor] = []
         self._first = None
         if policy_factory is None:
             if model is not None:
@@ -175,7 +180,10 @@ class InternVLAN1Agent:
                 assert so.output_latent is not None, f"S2 output should be either action or latent, but got neither! {so}"
                 s1_jobs.append(i)
         if s1_jobs:
+            self._tables = []
             self._run_s1([(envs[i], obs[i]) for i in s1_jobs])
+            if self._tables:
+                self.last_action_table = self._tables[0] if len(self._tables) == 1 else torch.cat(self._tables, 0)
             for i in s1_jobs:
                 e = envs[i]
                 idx = e.s1_output.idx
@@ -377,9 +385,7 @@ class InternVLAN1Agent:
             rgb_t, dep_t = self._prep_s1_device(jobs)
             lats = [e.s2_output.output_latent for e, _ in jobs]
             traj = model.generate_traj(traj_latents=torch.cat(lats, 0), images_dp=rgb_t.to(model.device), depths_dp=dep_t.to(model.device))
-            S = traj.shape[0] // len(jobs)
-            for k, (e, _) in enumerate(jobs):
-                e.s1_output = e.policy.actions_from_traj(traj[k * S:(k + 1) * S])
+            self._s1_outputs(jobs, traj)
             return
         rgbs, depths, lats = [], [], []
         for e, o in jobs:
@@ -396,6 +402,16 @@ class InternVLAN1Agent:
         rgb_t = torch.from_numpy(np.stack(rgbs)).to(model.device, torch.float32)
         dep_t = torch.from_numpy(np.stack(depths)).to(model.device, torch.float32)
         traj = model.generate_traj(traj_latents=torch.cat(lats, 0), images_dp=rgb_t, depths_dp=dep_t)
+        self._s1_outputs(jobs, traj)
+
+    def _s1_outputs(self, jobs, traj):
+        """per-env S1Output from generate_traj's [S * n, T, 3]: one traj_to_actions per env on the host, or (device_actions) one launch for all."""
+        if self.device_actions:
+            pol = jobs[0][0].policy
+            for (e, _), out in zip(jobs, pol.actions_from_traj_batch(traj, len(jobs))):
+                e.s1_output = out
+            self._tables.append(pol.last_action_table)
+            return
         S = traj.shape[0] // len(jobs)
         for k, (e, _) in enumerate(jobs):
             e.s1_output = e.policy.actions_from_traj(traj[k * S:(k + 1) * S])

@@ -3,7 +3,8 @@ engines: the GPU-less-testable functional driver of the dual system (SURVEY.md 8
 
 Same surface: `InternVLAN1AsyncAgent(args)` with args.{device, model_path, resize_w, resize_h, num_history, plan_step_gap},
 `reset()`, `step(rgb, depth, pose, instruction, intrinsic, look_down=False) -> S2Output`, `step_s2`, `step_s1`, `step_no_infer`,
-`trajectory_tovw`. One call of `step` = one camera frame: System-2 runs when the plan is older than PLAN_STEP_GAP frames, on a look-down
+`trajectory_tovw`; args.device_actions (optional, default False) takes the continuous trajectory from the device kernel. One call of
+`step` = one camera frame: System-2 runs when the plan is older than PLAN_STEP_GAP frames, on a look-down
 frame, or when nothing is pending (:127-139); otherwise the frame only extends the history. A discrete answer is returned once as
 `output_action`; a pixel goal leaves a latent behind and every following frame returns System-1's continuous trajectory
 (`traj_to_actions(..., use_discrate_action=False)`, :141-162) until the next System-2 call.
@@ -35,6 +36,7 @@ class InternVLAN1AsyncAgent:
         self.model, self.processor = self.net.model, self.net.processor
         self.resize_w, self.resize_h, self.num_history = kw["resize_w"], kw["resize_h"], kw["num_history"]
         self.PLAN_STEP_GAP = g("plan_step_gap", 8)
+        self.device_actions = bool(g("device_actions", False))
         self.reset()
 
     # ---- state of the reference object, kept on the shared policy
@@ -89,7 +91,15 @@ class InternVLAN1AsyncAgent:
         elif self.output_latent is not None:
             rgbs, depths = self._s1_inputs(rgb, depth)
             trajectories = self.step_s1(self.output_latent, rgbs, depths)
-            out.output_trajectory = traj_to_actions(trajectories, use_discrate_action=False)
+            if self.device_actions:
+                # the mean trajectory of ina_traj_actions: bit-equal to the numpy result, one [T + 1, 2] f64 copy instead of the [S, T, 3] samples
+                from . import ops
+
+                mean = torch.empty((1, trajectories.shape[-2] + 1, 2), dtype=torch.float64, device=trajectories.device)
+                ops.traj_actions(trajectories, 1, 1, traj_out=mean)
+                out.output_trajectory = mean[0].cpu().numpy()
+            else:
+                out.output_trajectory = traj_to_actions(trajectories, use_discrate_action=False)
         return out
 
     def _s1_inputs(self, rgb, depth):

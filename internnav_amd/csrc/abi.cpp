@@ -183,6 +183,11 @@ int ina_memory_gather(void* out, int64_t out_env_stride, float* ring, const floa
                                     reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_traj_actions(void* traj, int32_t traj_dtype, int32_t B, int32_t S, int32_t T, int32_t* actions, int32_t max_actions, int32_t* count,
+                     double* traj_out, int32_t scale_in_place, void* stream) {
+    return ina_launch_traj_actions(traj, traj_dtype, B, S, T, actions, max_actions, count, traj_out, scale_in_place, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_gemm_select(const ina_gemm_args* args, int* kernel) {
     INA_REQUIRE(args != nullptr && kernel != nullptr, "gemm_select: null argument");
     GemmArgs p;

@@ -67,6 +67,8 @@ int ina_launch_kv_copy(int to_engine, const int64_t* layer_base, int n_layers, c
 int ina_launch_memory_gather(void* out, long out_env_stride, float* ring, const float* fresh, const float* blank, const float* pe,
                              const int32_t* env, const int32_t* head, const int32_t* count, int n, int max_envs, int M, int ntok, int C, int depth,
                              int stride, hipStream_t stream);                                                                // memory_gather.hip
+int ina_launch_traj_actions(void* traj, int traj_dtype, int B, int S, int T, int32_t* actions, int max_actions, int32_t* count, double* traj_out,
+                            int scale_in_place, hipStream_t stream);                                                         // traj_actions.hip
 int ina_launch_head3(const Head3Args& p, hipStream_t stream);
 int ina_launch_seqpool(const SeqpoolArgs& p, hipStream_t stream);
 int ina_launch_select(const SelectArgs& p, hipStream_t stream);

@@ -364,6 +364,27 @@ def memory_gather(out: torch.Tensor, ring: torch.Tensor, fresh: torch.Tensor, bl
     return out
 
 
+def traj_actions(traj: torch.Tensor, n_env: int, max_actions: int = 4, traj_out: Optional[torch.Tensor] = None,
+                 scale_in_place: bool = False):
+    """the action table of n_env envs from their sampled trajectories in one launch: what policy.traj_to_actions computes per env on the host
+    (include/internnav_amd.h: ina_traj_actions). traj f32|bf16 [n_env * S, T, 3] (generate_traj's layout, the S samples of an env contiguous) or
+    [n_env, S, T, 3]. Returns (actions int32 [n_env, max_actions] = the first max_actions entries of each env's list, zero-padded;
+    count int32 [n_env]), both on the device - nothing here waits for the GPU. traj_out f64 [n_env, T + 1, 2] receives the mean trajectory;
+    scale_in_place writes x / 4, y / 4 back into traj as the host function does."""
+    assert traj.is_cuda and traj.is_contiguous() and traj.dtype in _DT and traj.dim() in (3, 4) and traj.shape[-1] == 3
+    rows = traj.shape[0] if traj.dim() == 3 else traj.shape[0] * traj.shape[1]
+    assert n_env >= 1 and rows % n_env == 0 and (traj.dim() == 3 or traj.shape[0] == n_env), (tuple(traj.shape), n_env)
+    S, T = rows // n_env, traj.shape[-2]
+    if traj_out is not None:
+        assert traj_out.dtype == torch.float64 and traj_out.is_contiguous() and traj_out.shape == (n_env, T + 1, 2) and traj_out.device == traj.device
+    actions = torch.empty((n_env, max(int(max_actions), 0)), dtype=torch.int32, device=traj.device)
+    count = torch.empty((n_env,), dtype=torch.int32, device=traj.device)
+    rc = _lib.lib().ina_traj_actions(traj.data_ptr(), _DT[traj.dtype], n_env, S, T, actions.data_ptr(), int(max_actions), count.data_ptr(),
+                                     _ptr(traj_out), int(bool(scale_in_place)), _stream())
+    _lib.check(rc, "traj_actions")
+    return actions, count
+
+
 def goal_slots(out: torch.Tensor, L: int, kind: torch.Tensor, row: torch.Tensor, pos: Optional[torch.Tensor] = None, slot0: int = 1,
                nslots: int = 3, embed: Optional[torch.Tensor] = None, point=None, image=None, pixel=None) -> torch.Tensor:
     """goal embedding e of every env b by its kind (0 none: 0, 1 point: w @ point[row[b]] + bias, 2 image / 3 pixel: w @ mean of the

@@ -807,3 +807,16 @@ class InternVLAN1Net:
         else:
             action_list = chunk_token(dp_actions[np.random.choice(dp_actions.shape[0])])
         return S1Output(idx=[x for x in action_list if x != 0][:4])
+
+    def actions_from_traj_batch(self, dp_actions, n_env: int) -> List[S1Output]:
+        """`actions_from_traj` of n_env envs at once, on the device: dp_actions is generate_traj's [S * n_env, T, 3] (f32 | bf16, on the GPU); ONE
+        ina_traj_actions launch builds the [n_env, 4] int32 action table (kept as `last_action_table`, still on the device - what
+        dist.all_gather_actions exchanges) and ONE device-to-host copy of it replaces the copy of the trajectories and the per-env numpy loop.
+        Same S1Output per env as actions_from_traj; dp_actions is left as it is (the host function un-normalises its argument in place).
+        continuous_traj only: the chunk_token branch draws a sample with numpy's global generator and stays on the host."""
+        if not self.continuous_traj:
+            raise NotImplementedError("actions_from_traj_batch covers continuous_traj=True only; the chunk_token branch runs on the host (actions_from_traj)")
+        from . import ops
+
+        self.last_action_table, _ = ops.traj_actions(dp_actions, n_env, 4)
+        return [S1Output(idx=[x for x in row if x != 0]) for row in self.last_action_table.tolist()]
