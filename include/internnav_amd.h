@@ -61,7 +61,10 @@ int ina_prof_read_sub(int kind, int sub, double* ms_total, int64_t* launches, do
 
 /* ---- C[M,N] = epilogue(A[M,K] . W[N,K]^T): replaces every nn.Linear / patch-embed conv on the path
  *      (reference: torch.nn.Linear call sites, e.g. dinov2_layers/attention.py:46-48, mlp.py:27-29,
- *       navdp.py:94-100, internvla_n1_arch.py:129-134; transformers Qwen2.5-VL q/k/v/o/mlp projections). */
+ *       navdp.py:94-100, internvla_n1_arch.py:129-134; transformers Qwen2.5-VL q/k/v/o/mlp projections).
+ *      Epilogue order, the same in every kernel: +bias[n] -> act -> *colscale[n] -> *rowscale[m / rowscale_div] -> +R[m,n] -> store;
+ *      glu: act(gate + bias_g) * (up + bias_u) * rowscale. Refused (non-zero return): act outside INA_ACT_NONE_C .. INA_ACT_TANH_C, and
+ *      glu together with R or colscale - no kernel computes those. */
 typedef struct ina_gemm_args {
     const void* A;          /* bf16 [M,K], row stride lda (elements) */
     const void* W;          /* bf16 [N,K], row stride ldw */
@@ -72,7 +75,7 @@ typedef struct ina_gemm_args {
     const void* R;          /* residual [M,N] or NULL, dtype res_dtype, row stride ldr */
     int32_t M, N, K;
     int32_t lda, ldw, ldc, ldr;
-    int32_t act;            /* INA_ACT_* */
+    int32_t act;            /* INA_ACT_*_C (0 .. 6, INA_ACT_TANH_C included); any other value is refused */
     int32_t out_dtype;      /* INA_BF16 | INA_F32 */
     int32_t res_dtype;
     int32_t glu;            /* 1: W rows interleaved [gate16|up16], C = act(gate) * up */

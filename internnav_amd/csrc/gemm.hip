@@ -133,7 +133,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_nt_kernel(GemmArgs p) {
     bool staged = false;
     if constexpr (C::TN == 64 && C::LDS_BYTES >= size_t(WM * WN) * C::FM * 4096) {
         const size_t oes = p.out_dtype == INA_DT_BF16 ? 2 : 4, res = p.res_dtype == INA_DT_BF16 ? 2 : 4;
-        staged = ((uintptr_t)p.C % 16) == 0 && (p.ldc * oes) % 16 == 0 && (p.strideC * oes) % 16 == 0 &&
+        staged = ina_staged_act(p.act) && ((uintptr_t)p.C % 16) == 0 && (p.ldc * oes) % 16 == 0 && (p.strideC * oes) % 16 == 0 &&
                  (!p.R || (((uintptr_t)p.R % 16) == 0 && (p.ldr * res) % 16 == 0 && (p.strideR * res) % 16 == 0));
         if (staged) {
             // (the K loop ends with a barrier: every wave is done with the stage buffers, which become the transpose scratch)
@@ -180,6 +180,10 @@ int ina_plan_gemm(const GemmArgs& p_in, GemmArgs& p, int& kernel) {
     INA_REQUIRE(((uintptr_t)p.A % 16) == 0 && ((uintptr_t)p.W % 16) == 0 && ((uintptr_t)p.C % 8) == 0, "gemm: misaligned pointer");
     INA_REQUIRE(!p.R || p.ldr % 4 == 0, "gemm: ldr must be a multiple of 4");
     INA_REQUIRE(!p.glu || (p.N % 32 == 0), "gemm: GLU mode needs N %% 32 == 0");
+    INA_REQUIRE(p.act >= INA_ACT_NONE && p.act <= INA_ACT_TANH, "gemm: act=%d is not an activation code (0 .. %d)", p.act, (int)INA_ACT_TANH);
+    // GLU writes act(gate) * up * rowscale and nothing else: no kernel applies a colscale there, and a residual was added by one epilogue only
+    INA_REQUIRE(!p.glu || !p.R, "gemm: glu cannot be combined with a residual (R)");
+    INA_REQUIRE(!p.glu || !p.colscale, "gemm: glu cannot be combined with colscale");
     // tile selection: big tiles when the grid still fills the 256 CUs, smaller ones otherwise
     // skinny M: HBM-bound weight streaming with split-K (gemm_skinny.hip) instead of an under-filled tile grid
     INA_REQUIRE(!p.seg_stats || (p.M > 64 && !p.norm_gamma), "gemm: seg_stats exist in the row-panel kernels only (M >= 16384 rows; M=%d)", p.M);
@@ -272,8 +276,8 @@ int ina_plan_gemm(const GemmArgs& p_in, GemmArgs& p, int& kernel) {
     }
     if (cfg == 40) INA_REQUIRE(p.Wp && p.N % 16 == 0 && p.batch == 1, "gemm: tile config 40 needs the fragment-ordered copy of W (Wp), N %% 16 == 0, no batch (N=%d)", p.N);
     if (cfg == 39 || cfg == 40)
-        INA_REQUIRE(ina_gemm_w4_contract(p), "gemm: tile configs 39 / 40 (four-wave 256 x 256 tile) need K %% 64 == 0 and 16-byte aligned output / residual rows "
-                    "(M=%d N=%d K=%d ldc=%d)", p.M, p.N, p.K, p.ldc);
+        INA_REQUIRE(ina_gemm_w4_contract(p), "gemm: tile configs 39 / 40 (four-wave 256 x 256 tile) need K %% 64 == 0, 16-byte aligned output / residual rows "
+                    "and act none .. silu (M=%d N=%d K=%d ldc=%d act=%d)", p.M, p.N, p.K, p.ldc, p.act);
     INA_REQUIRE(!p.seg_stats || cfg == 34 || cfg == 35, "gemm: seg_stats (LayerNorm statistics of the produced rows) exist in the row-panel kernels only "
                 "(K = 384, plain epilogue, M >= 16384): this call would run tile config %d (M=%d N=%d K=%d)", cfg, p.M, p.N, p.K);
     if (cfg == 34 || cfg == 35)

@@ -90,7 +90,15 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs& p, f32x4 (&acc)[
 // epilogue removed). Here every wave drops one raw 16-row accumulator slab at a time into a private 4 KiB LDS scratch
 // (XOR-swizzled 16-byte chunks, conflict free) and re-reads it row-major: ALL epilogue math then runs in a small rolled loop on 8
 // (bf16 out) or 4 (f32 out) consecutive columns per lane, with vector bias / scale / residual loads and whole-line 16-byte stores.
-// Requires 16-byte aligned C (and R) rows and 64-column wave tiles; launchers fall back to the direct epilogue otherwise.
+// Requires 16-byte aligned C (and R) rows, 64-column wave tiles and one of its own activations; launchers fall back to the direct epilogue otherwise.
+// The activations of this epilogue are the four of the inference hot path, unrolled over a lane's columns. Every other code ina_act knows
+// (mish, tanh) runs on the DIRECT epilogue: launchers ask ina_staged_act() and the kernels' `staged` tests include it, so ina_act stays the
+// one list of codes. ina_act itself does not fit in here: its whole switch (erff, tanhf, log1pf) inside the rolled loop costs every staged
+// kernel registers on a branch they never take - measured on the policy step: -11 % with a copy per column, -6 % with one copy in a rolled
+// loop, and as a call the 192 x 256 and 128 x 128 tiles lose a wave of occupancy. A code that reaches ina_act_vec anyway poisons the
+// result (NaN) instead of passing the product through un-activated.
+__host__ __device__ inline bool ina_staged_act(int act) { return act >= INA_ACT_NONE && act <= INA_ACT_SILU; }
+
 template <int N>
 __device__ __forceinline__ void ina_act_vec(float (&v)[8], int act) {
     switch (act) {
@@ -110,7 +118,11 @@ __device__ __forceinline__ void ina_act_vec(float (&v)[8], int act) {
 #pragma unroll
             for (int q = 0; q < N; ++q) v[q] = ina_silu(v[q]);
             break;
-        default: break;
+        case INA_ACT_NONE: break;
+        default:
+#pragma unroll
+            for (int q = 0; q < N; ++q) v[q] = __builtin_nanf("");
+            break;
     }
 }
 

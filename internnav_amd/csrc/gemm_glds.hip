@@ -291,7 +291,7 @@ int launch_glds(const GemmArgs& p, hipStream_t stream) {
     using C = GldsCfg<BM, BN, WM, WN, NS>;
     // the LDS-transposed epilogue needs 16-byte aligned output (and residual) rows and 64-column wave tiles
     const size_t oes = p.out_dtype == INA_DT_BF16 ? 2 : 4, res = p.res_dtype == INA_DT_BF16 ? 2 : 4;
-    const bool staged = C::TN == 64 && ((uintptr_t)p.C % 16) == 0 && (p.ldc * oes) % 16 == 0 && (p.strideC * oes) % 16 == 0 &&
+    const bool staged = C::TN == 64 && ina_staged_act(p.act) && ((uintptr_t)p.C % 16) == 0 && (p.ldc * oes) % 16 == 0 && (p.strideC * oes) % 16 == 0 &&
                         (!p.R || (((uintptr_t)p.R % 16) == 0 && (p.ldr * res) % 16 == 0 && (p.strideR * res) % 16 == 0)) &&
                         ((p.glu ? p.N / 2 : p.N) % 4 == 0);
     static bool attr_done[2] = {false, false};
@@ -318,7 +318,7 @@ template <int BM, int BN, int WN>
 int launch_pp(const GemmArgs& p, hipStream_t stream) {
     using C = GldsCfg<BM, BN, 2, WN, 2>;
     const size_t oes = p.out_dtype == INA_DT_BF16 ? 2 : 4, res = p.res_dtype == INA_DT_BF16 ? 2 : 4;
-    const bool staged = C::TN == 64 && ((uintptr_t)p.C % 16) == 0 && (p.ldc * oes) % 16 == 0 && (p.strideC * oes) % 16 == 0 &&
+    const bool staged = C::TN == 64 && ina_staged_act(p.act) && ((uintptr_t)p.C % 16) == 0 && (p.ldc * oes) % 16 == 0 && (p.strideC * oes) % 16 == 0 &&
                         (!p.R || (((uintptr_t)p.R % 16) == 0 && (p.ldr * res) % 16 == 0 && (p.strideR * res) % 16 == 0)) &&
                         ((p.glu ? p.N / 2 : p.N) % 4 == 0);
     static bool attr_done[2] = {false, false};

@@ -444,7 +444,8 @@ int ina_launch_gemm_preshuffle(const void* W, void* Wp, int N, int K, long ldw, 
 }
 
 bool ina_gemm_w4_contract(const GemmArgs& p) {
-    // the kernel has the LDS-transposed epilogue only: whole 16-byte pieces of output (and residual) rows
+    // the kernel has the LDS-transposed epilogue only: whole 16-byte pieces of output (and residual) rows, one of that epilogue's activations
+    if (!ina_staged_act(p.act)) return false;
     const size_t oes = p.out_dtype == INA_DT_BF16 ? 2 : 4, res = p.res_dtype == INA_DT_BF16 ? 2 : 4;
     if ((double)p.M * p.lda * 2.0 >= 4.0e9 || (double)p.N * p.ldw * 2.0 >= 4.0e9) return false;   // 32-bit byte offsets of the DMA sources inside A / W
     return p.K % 64 == 0 && ((uintptr_t)p.C % 16) == 0 && (p.ldc * oes) % 16 == 0 && (p.strideC * oes) % 16 == 0 &&

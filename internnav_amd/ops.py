@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import AttnArgs, GemmArgs, NormArgs
 
-ACT = {None: 0, "none": 0, "gelu": 1, "gelu_erf": 1, "gelu_tanh": 2, "relu": 3, "silu": 4, "mish": 5}
+ACT = {None: 0, "none": 0, "gelu": 1, "gelu_erf": 1, "gelu_tanh": 2, "relu": 3, "silu": 4, "mish": 5, "tanh": 6}
 _DT = {torch.bfloat16: 0, torch.float32: 1}
 
 

@@ -12,7 +12,7 @@ import torch
 import torch.nn.functional as F
 
 BF, F32 = torch.bfloat16, torch.float32
-_ACT = {"gelu_erf": F.gelu, "gelu": F.gelu, "gelu_tanh": lambda t: F.gelu(t, approximate="tanh"), "relu": F.relu, "silu": F.silu, "tanh": torch.tanh,
+_ACT = {"gelu_erf": F.gelu, "gelu": F.gelu, "gelu_tanh": lambda t: F.gelu(t, approximate="tanh"), "relu": F.relu, "silu": F.silu, "tanh": torch.tanh, "mish": F.mish,
         None: lambda t: t, "none": lambda t: t}
 _SCALE = {None: lambda s: s, "id": lambda s: s, "one_plus": lambda s: 1 + s, "tanh": torch.tanh}
 
@@ -28,14 +28,28 @@ def _store(out, val, out_dtype=None, accumulate=False):
 
 
 # ---------------------------------------------------------------------------------------------------------------- ops.*
-def linear(x, w, bias=None, act=None, colscale=None, residual=None, out=None, out_dtype=BF, glu=False, batched=False, **_):
-    assert x.dtype == BF and w.dtype == BF and not glu
+def linear(x, w, bias=None, act=None, colscale=None, residual=None, out=None, out_dtype=BF, glu=False, batched=False, rowscale=None,
+           rowscale_div=1, prenorm=None, force_cfg=0, group_m=0, w_frag=None, seg_stats=None):
+    """the kernels' order: +bias -> act -> *colscale -> *rowscale[m // div] -> +residual; GLU: act(gate) * up * rowscale over [gate16 | up16] rows.
+    force_cfg / group_m / w_frag choose among kernels that compute the same thing and mean nothing here; seg_stats has no stand-in."""
+    assert w.dtype == BF and seg_stats is None and not (glu and (colscale is not None or residual is not None))
+    if prenorm is not None:
+        gamma, eps = prenorm
+        xf = x.float()
+        x = (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * gamma).to(BF)
+    assert x.dtype == BF
     y = x.float() @ w.float().t()
     if bias is not None:
         y = y + bias
-    if colscale is not None:
-        y = y * colscale
-    y = _ACT[act](y)
+    if glu:
+        y4 = y.reshape(*y.shape[:-1], y.shape[-1] // 32, 2, 16)
+        y = (_ACT[act](y4[..., 0, :]) * y4[..., 1, :]).reshape(*y.shape[:-1], y.shape[-1] // 2)
+    else:
+        y = _ACT[act](y)
+        if colscale is not None:
+            y = y * colscale
+    if rowscale is not None:
+        y = y * rowscale[torch.arange(y.shape[-2]) // rowscale_div][:, None]
     if residual is not None:
         y = y + residual.float()
     return _store(out, y, out_dtype if out is None else None)
