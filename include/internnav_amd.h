@@ -56,7 +56,7 @@ int ina_workspace_retired(void);
 int ina_prof_enable(int on);
 int ina_prof_read(int kind, double* ms_total, int64_t* launches, double* flops, double* bytes);
 /* the same tally restricted to one kernel of the class: sub = GEMM tile config id (18 = gemm_bf16_pp_kernel<256,256,4>, 21 = <192,256,4>,
- * 22 = gemm_bf16_glds_kernel<128,128,2,2,1>, 33 = gemm_bf16_glds_kernel<256,256,4,4,2>, 11 / 14 / 26 / 27 other LDS-DMA tiles, 1-5 gemm_bf16_nt_kernel tiles, 34 / 35 = gemm_bf16_rowpanel_kernel<8|4 waves>, 39 = gemm_bf16_w4_kernel<256> (four-wave 256x256 tile), 40 = gemm_bf16_w4p_kernel<256> (the same tile on fragment-ordered weights), 42 = dit_rowchain_kernel, 43 = gemm_dw_kernel) */
+ * 22 = gemm_bf16_glds_kernel<128,128,2,2,1>, 33 = gemm_bf16_glds_kernel<256,256,4,4,2>, 11 / 14 / 26 / 27 other LDS-DMA tiles, 1-5 gemm_bf16_nt_kernel tiles, 34 / 35 = gemm_bf16_rowpanel_kernel<8|4 waves>, 39 = gemm_bf16_w4_kernel<256> (four-wave 256x256 tile), 40 = gemm_bf16_w4p_kernel<256> (the same tile on fragment-ordered weights), 42 = dit_rowchain_kernel, 43 = gemm_dw_kernel; in class 4: 48 = the fp8-weight kernels of ina_gemm_w8) */
 int ina_prof_read_sub(int kind, int sub, double* ms_total, int64_t* launches, double* flops, double* bytes);
 
 /* ---- C[M,N] = epilogue(A[M,K] . W[N,K]^T): replaces every nn.Linear / patch-embed conv on the path
@@ -100,6 +100,16 @@ typedef struct ina_gemm_args {
                              * B fragments from it straight into registers (selected where cfg 39 would run; bit-equal results) */
 } ina_gemm_args;
 int ina_gemm_bf16(const ina_gemm_args* args, void* stream);
+/* The weight-streaming kernels (M <= 64; with norm_gamma: M <= 16, the fused input RMSNorm) on FP8 weights: W8 holds OCP e4m3 (e4m3fn) bytes,
+ * one per weight, and wexp[n] a power-of-two exponent per output row; the weight is q[n,k] * 2^wexp[n] (|wexp| <= 64), which is exactly a bf16
+ * number. The result is, bit for bit, ina_gemm_bf16's weight-streaming result (kernel 32 / 30) on those dequantised bf16 weights: same K
+ * decomposition and summation order, the row scale applied to the reduced fp32 sum before the bias. Half the weight bytes per launch.
+ * Packed row layout (K % 128 == 0): element k = step * 128 + s * 32 + g * 8 + j (s < 4, g < 4, j < 8) is byte step * 128 + g * 32 + s * 8 + j of
+ * its row; rows are ldw BYTES apart (ldw >= K, a multiple of 16). args->W is ignored; every other field means what it means for ina_gemm_bf16.
+ * Refused (non-zero, ina_last_error; checked before any HIP call): M > 64, K % 128 != 0, batch > 1, seg_stats, Wp, force_cfg > 0, norm_gamma
+ * with M > 16 / K > 4096 / N < 256, and the glu / R / colscale / act combinations ina_gemm_bf16 refuses.
+ * Profiler tally: class 4 (weight streaming), sub 48, with N * K + N weight bytes. */
+int ina_gemm_w8(const ina_gemm_args* args, const void* W8, const int8_t* wexp, void* stream);
 /* W bf16 [N,K] (row stride ldw) -> Wp bf16 [N*K]: fragment (n / 16, k / 32) is one contiguous KiB, element (n, k) at
  * ((n / 16) * (K / 32) + k / 32) * 512 + ((k % 32) / 8 * 16 + n % 16) * 8 + k % 8. Done once per weight at load time. */
 int ina_gemm_preshuffle(const void* W, void* Wp, int32_t N, int32_t K, int64_t ldw, void* stream);

@@ -158,6 +158,11 @@ int ina_gemm_bf16(const ina_gemm_args* args, void* stream) {
     return ina_launch_gemm(*args, reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_gemm_w8(const ina_gemm_args* args, const void* W8, const int8_t* wexp, void* stream) {
+    INA_REQUIRE(args != nullptr, "gemm_w8: null args");
+    return ina_launch_gemm_w8(*args, W8, wexp, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_gemm_preshuffle(const void* W, void* Wp, int32_t N, int32_t K, int64_t ldw, void* stream) {
     return ina_launch_gemm_preshuffle(W, Wp, N, K, (long)ldw, reinterpret_cast<hipStream_t>(stream));
 }

@@ -142,6 +142,83 @@ def gemm_preshuffle(w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torc
     return out
 
 
+# ---- FP8 weights of the weight-streaming GEMMs (csrc/gemm_skinny_w8.hip): OCP e4m3 bytes + a power-of-two scale per output row
+W8_MAX = 448.0          # largest finite e4m3fn value
+W8_EXP_RANGE = 64       # |exponent| bound: 2^e stays a normal fp32 / bf16 with room to spare
+
+
+def w8_pack(q: torch.Tensor) -> torch.Tensor:
+    """uint8 [N, K] in natural k order -> the kernels' row layout (K % 128 == 0): element k = step * 128 + s * 32 + g * 8 + j (MFMA step s, lane
+    group g, lane element j) moves to byte step * 128 + g * 32 + s * 8 + j of its row, so a lane's 32 bytes of a K step are contiguous."""
+    assert q.dtype == torch.uint8 and q.dim() == 2 and q.shape[1] % 128 == 0, "w8 layout: uint8 [N, K] with K % 128 == 0"
+    N, K = q.shape
+    return q.reshape(N, K // 128, 4, 4, 8).transpose(2, 3).reshape(N, K).contiguous()
+
+
+def w8_unpack(p: torch.Tensor) -> torch.Tensor:
+    """inverse of w8_pack (the permutation swaps two axes of equal length: it is its own inverse)"""
+    return w8_pack(p)
+
+
+def w8_quantize(w: torch.Tensor):
+    """w bf16 [N, K] (K % 128 == 0) -> (w8 uint8 [N, K] packed e4m3fn bytes, wexp int8 [N], w_deq bf16 [N, K]).
+
+    Row n is stored as q = e4m3fn_rne(w / 2^e_n) with e_n the smallest exponent for which the row's amax fits 448 (an all-zero row: 0),
+    clamped to [-64, 64]; w_deq = q * 2^e_n is exact in bf16 - it is the model the fp8 kernels compute, and w8_quantize(w_deq)[2] == w_deq."""
+    assert w.dtype == torch.bfloat16 and w.dim() == 2 and w.shape[1] % 128 == 0, "w8_quantize: bf16 [N, K] with K % 128 == 0"
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    # amax = m * 2^x with m in [0.5, 1), 448 = 0.875 * 2^9: amax <= 448 * 2^e  <=>  e >= x - 9 (m <= 0.875) or x - 8 (exact: no log2 rounding)
+    m, x = torch.frexp(amax)
+    e = torch.where(m <= 0.875, x - 9, x - 8)
+    e = torch.where(amax == 0, torch.zeros_like(e), e).clamp(-W8_EXP_RANGE, W8_EXP_RANGE).to(torch.int32)
+    scaled = torch.ldexp(wf, (-e)[:, None]).clamp(-W8_MAX, W8_MAX)      # (torch's fp8 cast does not saturate: clamp first)
+    q = scaled.to(torch.float8_e4m3fn)
+    w_deq = torch.ldexp(q.float(), e[:, None]).to(torch.bfloat16)
+    return w8_pack(q.view(torch.uint8)), e.to(torch.int8).contiguous(), w_deq.contiguous()
+
+
+def linear_w8(x: torch.Tensor, w8: torch.Tensor, wexp: torch.Tensor, bias: Optional[torch.Tensor] = None, act=None,
+              colscale: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None, out_dtype=torch.bfloat16, glu: bool = False,
+              rowscale: Optional[torch.Tensor] = None, rowscale_div: int = 1, prenorm=None) -> torch.Tensor:
+    """`linear` on FP8 weights for at most 64 rows (prenorm: 16): w8 uint8 [N, K] packed (w8_quantize / w8_pack), wexp int8 [N].
+    Bit for bit the weight-streaming result of linear(x, w_deq, ...) on the dequantised weights, at half the weight bytes."""
+    assert (x.dtype == torch.bfloat16 or prenorm is not None) and w8.dtype == torch.uint8 and wexp.dtype == torch.int8
+    assert w8.dim() == 2 and w8.stride(1) == 1 and wexp.is_contiguous() and wexp.numel() == w8.shape[0]
+    N, K = w8.shape
+    n_out = N // 2 if glu else N
+    lead = x.shape[:-1]
+    x2 = _as2d(x)
+    assert x2.dim() == 2 and x.shape[-1] == K, f"K mismatch {tuple(w8.shape)} vs {tuple(x.shape)}"
+    M = x2.shape[0]
+    if out is None:
+        out = torch.empty(*lead, n_out, dtype=out_dtype, device=x.device)
+    o2 = _as2d(out)
+    assert o2.shape == (M, n_out), f"out {tuple(o2.shape)} vs {(M, n_out)}"
+    a = GemmArgs()
+    a.A, a.C = x2.data_ptr(), o2.data_ptr()
+    a.lda, a.ldc = x2.stride(0), o2.stride(0)
+    a.batch = 1
+    if residual is not None:
+        r2 = _as2d(residual)
+        assert r2.shape == (M, n_out)
+        a.R, a.ldr, a.res_dtype = r2.data_ptr(), r2.stride(0), _DT[r2.dtype]
+    a.ldw = w8.stride(0)
+    a.bias, a.colscale, a.rowscale = _ptr(_f32(bias)), _ptr(_f32(colscale)), _ptr(_f32(rowscale))
+    a.M, a.N, a.K = M, N, K
+    a.act = ACT[act] if not isinstance(act, int) else act
+    a.out_dtype = _DT[out.dtype]
+    a.glu = 1 if glu else 0
+    a.rowscale_div = rowscale_div
+    if prenorm is not None:
+        gamma, eps = prenorm
+        assert x.dtype in (torch.bfloat16, torch.float32) and gamma.dtype == torch.float32 and gamma.is_contiguous() and gamma.numel() == K
+        a.norm_gamma, a.norm_eps, a.a_dtype = gamma.data_ptr(), float(eps), _DT[x.dtype]
+    _lib.check(_lib.lib().ina_gemm_w8(C.byref(a), w8.data_ptr(), wexp.data_ptr(), _stream()), "gemm_w8")
+    return out
+
+
 def attention_rope_ok(Lq: int, Lk: int, H: int, Hkv: int, D: int) -> bool:
     """shapes whose attention launch can carry the rotary embedding + KV append of its new tokens (the one-launch decode kernel of the d = 128
     heads; csrc/attention.hip ina_launch_attention)"""

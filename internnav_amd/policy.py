@@ -188,7 +188,7 @@ class InternVLAN1ForCausalLM:
     def __init__(self, weights, qwen_cfg: dict, system1: str = "nextdit_async", s1_cfg: Optional[dict] = None,
                  device="cuda:0", max_envs: int = 16, max_seq_len: Optional[int] = None, max_patches: Optional[int] = None,
                  max_s2_seqs: Optional[int] = None, num_history: int = 8, resize_w: int = 384, resize_h: int = 384,
-                 cam_w: int = 640, cam_h: int = 480):
+                 cam_w: int = 640, cam_h: int = 480, w8_decode: bool = False):
         """Engine capacity defaults to the longest prompt the reference's harness can build for (num_history, resize, camera size):
         see `s2_capacity`; exceeding it raises `CapacityError` (never a silent STOP)."""
         self.device = torch.device(device)
@@ -200,7 +200,7 @@ class InternVLAN1ForCausalLM:
         n_s2 = max_s2_seqs or max_envs   # System-2 runs on micro-batches of the envs whose plan expired (agent / bench schedule)
         cap_seq, cap_patches = s2_capacity(num_history, resize_w, resize_h, cam_w, cam_h, n_query=qwen_cfg["n_query"])
         self.qwen = QwenVLEngine(weights, qwen_cfg, device, max_seqs=n_s2, max_seq_len=max_seq_len or cap_seq,
-                                 max_patches=max_patches or n_s2 * cap_patches)
+                                 max_patches=max_patches or n_s2 * cap_patches, w8_decode=w8_decode)
         if "nextdit" in system1:
             # the DiT's geometry (width, depth, heads, FFN width) is not in config.json - NextDiTCrossAttnConfig is constructed in code
             # (internvla_n1_arch.py:127-131) and its FFN width depends on the diffusers release (synthetic.lumina_ffn_width): read it off
@@ -568,13 +568,14 @@ class InternVLAN1Net:
     @classmethod
     def _load(cls, ms: dict):
         """model + processor for a model_settings dict, loaded once per (checkpoint, device) and shared afterwards."""
-        key = (str(ms["model_path"]), str(ms.get("device", "cuda:0")))
+        key = (str(ms["model_path"]), str(ms.get("device", "cuda:0")), bool(ms.get("w8_decode", False)))
         if key not in cls._shared:
             n_env = int(ms.get("env_num", 1) or 1)
             model = InternVLAN1ForCausalLM.from_pretrained(
                 ms["model_path"], torch_dtype=torch.bfloat16, attn_implementation="flash_attention_2", device_map={"": ms.get("device", "cuda:0")},
                 max_envs=max(n_env, int(ms.get("max_envs", 1))), max_s2_seqs=ms.get("max_s2_seqs"), num_history=ms.get("num_history", 8),
-                resize_w=ms.get("resize_w", 384), resize_h=ms.get("resize_h", 384), cam_w=ms.get("width", 640), cam_h=ms.get("height", 480))
+                resize_w=ms.get("resize_w", 384), resize_h=ms.get("resize_h", 384), cam_w=ms.get("width", 640), cam_h=ms.get("height", 480),
+                w8_decode=bool(ms.get("w8_decode", False)))      # System-2 single-token passes on FP8 weights (QwenVLEngine(w8_decode=True))
             cls._shared[key] = (model.eval(), cls.load_processor(ms["model_path"]))
         return cls._shared[key]
 

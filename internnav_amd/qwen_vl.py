@@ -233,6 +233,22 @@ class EngineKVCache:
         return c
 
 
+W8_DECODER_KEYS = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
+                   "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
+
+
+def w8_roundtrip_state_dict(sd, cfg: dict) -> dict:
+    """the checkpoint an engine built with w8_decode=True computes: q / k / v / o / gate / up / down of every decoder layer and lm_head replaced
+    by their e4m3 * 2^e round trip (ops.w8_quantize of the bf16 weight: the scale is per output row, so fusing or interleaving rows afterwards
+    changes nothing); every other tensor is passed through. For tests, and for evaluating the quantised model elsewhere."""
+    names = {f"model.layers.{i}.{k}" for i in range(cfg["t_layers"]) for k in W8_DECODER_KEYS} | {"lm_head.weight"}
+    out = {}
+    for k in sd.keys():
+        v = sd[k]
+        out[k] = ops.w8_quantize(v.to(torch.bfloat16).contiguous())[2].to(v.dtype) if k in names else v
+    return out
+
+
 def _interleave16(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     n, k = a.shape
     return torch.stack([a.view(n // 16, 16, k), b.view(n // 16, 16, k)], dim=1).reshape(2 * n, k).contiguous()
@@ -246,7 +262,7 @@ class QwenVLEngine:
     """weights: mapping key -> tensor (a state dict, or a lazy provider that materialises tensors on the device)."""
 
     def __init__(self, weights, cfg: dict, device="cuda:0", max_seqs: int = 16, max_seq_len: int = 1024, max_patches: int = 16 * 3136,
-                 frag_weights: Optional[bool] = None):
+                 frag_weights: Optional[bool] = None, w8_decode: bool = False):
         dev = torch.device(device)
         bf, f32 = torch.bfloat16, torch.float32
         self.cfg, self.device = cfg, dev
@@ -323,10 +339,17 @@ class QwenVLEngine:
         # that run the four-wave 256 x 256 tile then fetch their B fragments straight from global memory into registers (tile config 40,
         # gemm_w4.hip: half the LDS-DMA pieces and fragment reads per stage; bit-equal); the single-token passes keep streaming the row-major copy
         self.frag_weights = torch.device(dev).type == "cuda" if frag_weights is None else bool(frag_weights)
-        if self.frag_weights:
-            self.refresh_frag_weights()
         self.norm_w = f("model.norm.weight")
         self.lm_head = w("lm_head.weight")
+        # w8_decode: the decoder projections and lm_head rounded to e4m3 * 2^e per output row (ops.w8_quantize). The bf16 tensors then hold the
+        # dequantised values - the model every pass computes - and the GEMMs of at most SKINNY_GEMM_MAX_ROWS rows stream the fp8 bytes instead
+        # (ops.linear_w8: half the weight bytes, the same bits as the bf16 weight-streaming kernels on the dequantised weights)
+        self.w8_decode = False
+        self.lm_head8 = None
+        if w8_decode:
+            self.refresh_w8_weights()          # (rebuilds the fragment-ordered copies from the dequantised weights)
+        elif self.frag_weights:
+            self.refresh_frag_weights()
         self.latent_q = W["model.latent_queries"].to(device=dev, dtype=bf).reshape(-1, H).contiguous()
         rows = max_seqs * max_seq_len
         self.x_in = torch.empty(rows, H, dtype=bf, device=dev)
@@ -437,6 +460,41 @@ class QwenVLEngine:
             for k in ("qkv_wf", "gu_wf", "down_wf"):
                 L.pop(k, None)
 
+    W8_LAYER_WEIGHTS = ("qkv_w", "o_w", "gu_w", "down_w")
+
+    def refresh_w8_weights(self):
+        """(re)quantise q|k|v, o, gate|up, down of every decoder layer and lm_head to e4m3 with a power-of-two scale per output row - at load
+        (w8_decode=True), and after anything that replaces or updates one of these weights in place. The bf16 tensors are overwritten IN PLACE
+        with the dequantised values (twins and the prefill keep reading them; quantising them again changes nothing), the packed fp8 bytes
+        and the exponents are kept beside them (+ 7 GB at the 7B geometry) and the fragment-ordered copies are rebuilt. Vision tower,
+        embeddings, norms and biases are untouched."""
+        for L in self.layers:
+            for k in self.W8_LAYER_WEIGHTS:
+                w8, e, wd = ops.w8_quantize(L[k])
+                L[k].copy_(wd)
+                L[k + "8"] = (w8, e)
+        w8, e, wd = ops.w8_quantize(self.lm_head)
+        self.lm_head.copy_(wd)
+        self.lm_head8 = (w8, e)
+        self.w8_decode = True
+        if self.frag_weights:
+            self.refresh_frag_weights()
+
+    def drop_w8_weights(self):
+        """release the fp8 copies: the single-token passes stream the (dequantised) bf16 weights again - the same model, the same bits"""
+        self.w8_decode = False
+        self.lm_head8 = None
+        for L in self.layers:
+            for k in self.W8_LAYER_WEIGHTS:
+                L.pop(k + "8", None)
+
+    def _linear(self, x, L: dict, k: str, w8: bool, **kw):
+        """one decoder projection: the fp8 weight stream where this pass uses it (same bits), else the bf16 kernels"""
+        if w8:
+            kw.pop("w_frag", None)
+            return ops.linear_w8(x, *L[k + "8"], **kw)
+        return ops.linear(x, L[k], **kw)
+
     # ------------------------------------------------------------------------------------------------ text model
     def _phase(self, B: int, S: int, pos3: np.ndarray, cache_pos0, k_len: Optional[np.ndarray] = None, b0: int = 0) -> dict:
         """host side of one pass of the decoder stack over B x S new tokens: 3-D position ids, cache rows, key lengths.
@@ -474,27 +532,29 @@ class QwenVLEngine:
         if fuse_rope:
             kn4 = qkv[:, nh * hd:(nh + nkv) * hd].view(B, S, nkv, hd)
             vn4 = qkv[:, (nh + nkv) * hd:].view(B, S, nkv, hd)
+        # w8_decode: every GEMM of this pass that would run the bf16 weight-streaming kernels reads the fp8 copy instead
+        w8 = self.w8_decode and rows <= SKINNY_GEMM_MAX_ROWS
         for li, L in enumerate(self.layers):
             src = x_in if li == 0 else x
             wf = (lambda k, L=L: L.get(k)) if (self.frag_weights and rows > SKINNY_GEMM_MAX_ROWS) else (lambda k: None)
             if fused_norm:
-                ops.linear(src, L["qkv_w"], bias=L["qkv_b"], out=qkv, prenorm=(L["n1"], 1e-6))
+                self._linear(src, L, "qkv_w", w8, bias=L["qkv_b"], out=qkv, prenorm=(L["n1"], 1e-6))
             else:
                 ops.norm(src, L["n1"], None, eps=1e-6, rms=True, out=h)
-                ops.linear(h, L["qkv_w"], bias=L["qkv_b"], out=qkv, w_frag=wf("qkv_wf"))
+                self._linear(h, L, "qkv_w", w8, bias=L["qkv_b"], out=qkv, w_frag=wf("qkv_wf"))
             if not fuse_rope:
                 # m-rope on q (in place) and k, and the KV-cache append (rotated k | v -> cache row of every token) in ONE launch
                 ops.rope(qkv, cos, sin, heads=nh + nkv, D=hd, col0=0, rows=rows, kv_out=L["kv"], kv_dst=ph["rows"], kv_head0=nh, v_heads=nkv)
             kv4 = L["kv"].view(self.B_max, Smax, 2, nkv, hd)[b0:b0 + B, : ph["Lk"]]
             ops.attention(q4, kv4[:, :, 0], kv4[:, :, 1], causal=True, out=att.view(B, S, nh, hd), k_len=ph["k_len"],
                           rope=(cos, sin, kn4, vn4) if fuse_rope else None)
-            ops.linear(att, L["o_w"], residual=src, out=x)
+            self._linear(att, L, "o_w", w8, residual=src, out=x)
             if fused_norm:
-                ops.linear(x, L["gu_w"], act="silu", glu=True, out=ff, prenorm=(L["n2"], 1e-6))
+                self._linear(x, L, "gu_w", w8, act="silu", glu=True, out=ff, prenorm=(L["n2"], 1e-6))
             else:
                 ops.norm(x, L["n2"], None, eps=1e-6, rms=True, out=h)
-                ops.linear(h, L["gu_w"], act="silu", glu=True, out=ff, w_frag=wf("gu_wf"))
-            ops.linear(ff, L["down_w"], residual=x, out=x, w_frag=wf("down_wf"))
+                self._linear(h, L, "gu_w", w8, act="silu", glu=True, out=ff, w_frag=wf("gu_wf"))
+            self._linear(ff, L, "down_w", w8, residual=x, out=x, w_frag=wf("down_wf"))
             if self.tap is not None:
                 self.tap("llm", li, x)
 
@@ -506,7 +566,10 @@ class QwenVLEngine:
             ops.norm(self.xl[:B], self.norm_w, None, eps=1e-6, rms=True, out=self.hl[:B], rows=B)
         else:
             ops.norm(self.x[: B * S], self.norm_w, None, eps=1e-6, rms=True, out=self.hl[:B], rows=B, in_map=(1, S, row_in_seq))
-        ops.linear(self.hl[:B], self.lm_head, out=self.logits[:B])     # (152064 columns: one wave per 16-column tile owns all of K)
+        if self.w8_decode and B <= SKINNY_GEMM_MAX_ROWS:
+            ops.linear_w8(self.hl[:B], *self.lm_head8, out=self.logits[:B])
+        else:
+            ops.linear(self.hl[:B], self.lm_head, out=self.logits[:B])     # (152064 columns: one wave per 16-column tile owns all of K)
         ops.argmax_rows(self.logits[:B], self.next_tok[:B])
 
     # ---- plan / run: all host work up front, then a pure launch sequence (hipGraph capturable)

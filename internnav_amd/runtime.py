@@ -92,6 +92,16 @@ def prof_read_gemm_kernels() -> Dict[str, dict]:
     return out
 
 
+W8_PROF = (4, 48)   # (class, sub) of the fp8-weight launches (ina_gemm_w8) inside the weight-streaming class
+
+
+def prof_read_w8() -> dict:
+    """the fp8-weight launches (ops.linear_w8) of the weight-streaming class on their own; bytes count N * K + N per weight, not 2 * N * K."""
+    ms, n, fl, by = C.c_double(), C.c_int64(), C.c_double(), C.c_double()
+    _lib.check(_lib.lib().ina_prof_read_sub(W8_PROF[0], W8_PROF[1], C.byref(ms), C.byref(n), C.byref(fl), C.byref(by)), "prof_read_sub")
+    return dict(ms=ms.value, launches=n.value, flops=fl.value, bytes=by.value)
+
+
 def prof_read() -> Dict[str, dict]:
     """Totals per kernel class since prof_enable(True): summed event-pair time (ms), launches, algorithmic FLOPs and bytes."""
     out = {}
