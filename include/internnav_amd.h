@@ -678,7 +678,8 @@ int ina_gemm_dw(const ina_gemm_dw_args* args, void* stream);
 /* backward of ina_attention_bf16 (dense layouts only): f describes the forward call (Q, K, V, O and their strides);
  * dO has O's strides. dQ pass writes lse / delta [B, H, Lq] f32, the dK / dV pass (optional) reads them. dK / dV are indexed by the
  * QUERY head (sum the heads of a GQA group afterwards) and hold the key rows [kv_row0, Lk); kv_row0 = -1: the last Lq key rows of every
- * sequence (k_len - Lq .. k_len: the query rows' own keys in a cached causal pass). */
+ * sequence (max(0, k_len - Lq) .. k_len: the query rows' own keys in a cached causal pass; min(Lq, Lk) rows). Every row of dK / dV is stored:
+ * dk / dv rows of keys at or past k_len are written as zero. */
 typedef struct ina_attn_bwd_args {
     ina_attn_args f;
     const void* dO; void* dQ; void* dK; void* dV;
@@ -687,7 +688,7 @@ typedef struct ina_attn_bwd_args {
     int32_t kv_row0;
     int32_t nsplit;         /* > 1: split the keys of the dQ pass over nsplit workgroups per query tile (few query rows, long key axis):
                              * dQ is then accumulated with f32 atomics into dq32 (dense [B, Lq, H, D], zeroed by the caller; dQ is not written) */
-    float* part;            /* f32 scratch [B, H, nsplit, 2, Lq] (nsplit > 1) */
+    float* part;            /* f32 scratch [B, H, ceil(Lk / 64), 2, Lq] (nsplit > 1): the statistics of every 64-key block */
     float* dq32;
     int32_t stage, _pad;    /* internal (set by the launcher) */
 } ina_attn_bwd_args;

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_kernel(AttnBwdArgs a) {
 
     if constexpr (MODE == 0) {
         // few query rows against a long key axis (the latent-query rows of the LLM): the keys are split over gridDim.x / q-tiles workgroups.
-        //   stage 1: every split writes its partial softmax statistics (m, l);  stage 2: combine them, dS / dQ of the split's keys, fp32
+        //   stage 1: every split writes the softmax statistics (m, l) of its key blocks;  stage 2: merge them, dS / dQ of the split's keys, fp32
         //   atomics into dq32.  stage 0 (nsplit 1) = both passes over all keys in one launch, bf16 dQ stored directly.
         const int nsplit = a.nsplit > 1 ? a.nsplit : 1;
         const int qt0 = (blockIdx.x / nsplit) * (NW * 16), split = blockIdx.x % nsplit;
@@ -112,13 +112,20 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_kernel(AttnBwdArgs a) {
         if (p.causal) kv_end = min(len_k, min(qt0 + NW * 16, len_q) + causal_shift);
         int ks = 0, ke = kv_end;
         if (nsplit > 1) {
-            const int nblk = (kv_end + CB - 1) / CB, per = (nblk + nsplit - 1) / nsplit;
+            const int nblk = (max(kv_end, 0) + CB - 1) / CB, per = (nblk + nsplit - 1) / nsplit;
             ks = min(kv_end, split * per * CB);
             ke = min(kv_end, ks + per * CB);
         }
-        float* pm = a.part + (((size_t)b * p.H + h) * nsplit) * 2 * p.Lq;   // [split][m | l][Lq]
-        // ---- pass 1: softmax statistics
+        float* pm = a.part + (((size_t)b * p.H + h) * ((p.Lk + CB - 1) / CB)) * 2 * p.Lq;   // [key block][m | l][Lq]
+        // ---- pass 1: softmax statistics. Every 64-key block gives (m, l) relative to its own maximum and the blocks are merged in key order
+        // by the same expression in every stage, so lse - and with it P of the dK / dV pass - has the same bits whatever the split.
         float m_run = -INFINITY, l_run = 0.f;
+        auto merge = [&](float m2, float l2) {
+            const float m_new = fmaxf(m_run, m2);
+            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
+            l_run = fmaf(l_run, exp2f(m_run - m_use), l2 * exp2f(m2 - m_use));
+            m_run = m_new;
+        };
         if (a.stage != 2) {
           for (int kv0 = ks; kv0 < ke; kv0 += CB) {
             __syncthreads();
@@ -141,36 +148,32 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_kernel(AttnBwdArgs a) {
             }
             mx = fmaxf(mx, __shfl_xor(mx, 16));
             mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float m_new = fmaxf(m_run, mx);
-            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
+            const float b_use = (mx == -INFINITY) ? 0.f : mx;
             float rs = 0.f;
 #pragma unroll
             for (int t = 0; t < NST; ++t)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) rs += exp2f(s[t][r] - m_use);
+                for (int r = 0; r < 4; ++r) rs += exp2f(s[t][r] - b_use);
             rs += __shfl_xor(rs, 16);
             rs += __shfl_xor(rs, 32);
-            l_run = l_run * exp2f(m_run - m_use) + rs;
-            m_run = m_new;
+            if (a.stage == 1) {
+                if (live && g == 0) {
+                    pm[(size_t)(kv0 / CB) * 2 * p.Lq + q_abs] = mx;
+                    pm[(size_t)(kv0 / CB) * 2 * p.Lq + p.Lq + q_abs] = rs;
+                }
+            } else {
+                merge(mx, rs);
+            }
           }
         }
         if (a.stage == 1) {
-            if (live && g == 0) {
-                pm[(size_t)split * 2 * p.Lq + q_abs] = m_run;
-                pm[(size_t)split * 2 * p.Lq + p.Lq + q_abs] = l_run;
-                if (split == 0) dlt[q_abs] = dl;
-            }
+            if (live && g == 0 && split == 0) dlt[q_abs] = dl;
             return;
         }
         if (a.stage == 2) {
-            for (int sidx = 0; sidx < nsplit; ++sidx) {
-                const float m2 = live ? pm[(size_t)sidx * 2 * p.Lq + q_abs] : -INFINITY;
-                const float l2 = live ? pm[(size_t)sidx * 2 * p.Lq + p.Lq + q_abs] : 0.f;
-                const float m_new = fmaxf(m_run, m2);
-                const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-                l_run = l_run * exp2f(m_run - m_use) + l2 * exp2f(m2 - m_use);
-                m_run = m_new;
-            }
+            const int nblk = (max(kv_end, 0) + CB - 1) / CB;     // every block of [0, kv_end) was written by exactly one split
+            for (int blk = 0; blk < nblk; ++blk)
+                merge(live ? pm[(size_t)blk * 2 * p.Lq + q_abs] : -INFINITY, live ? pm[(size_t)blk * 2 * p.Lq + p.Lq + q_abs] : 0.f);
         }
         const float lse2 = (l_run > 0.f) ? m_run + log2f(l_run) : INFINITY;
         if (live && g == 0 && split == 0) { lse[q_abs] = lse2; dlt[q_abs] = dl; }
@@ -241,9 +244,25 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_kernel(AttnBwdArgs a) {
     } else {
         const int row0 = a.kv_row0 < 0 ? max(0, len_k - len_q) : a.kv_row0;   // -1: the last Lq keys of every sequence (ragged k_len)
         const int kt0 = row0 + blockIdx.x * (NW * 16);
-        if (kt0 >= len_k) return;
         const int k_abs = kt0 + wave * 16 + lq;
         const bool live = k_abs < len_k;
+        // the gradient of a masked-out key is zero: every output row of the grid (the launcher's `rows`) is stored, the rows of keys at or
+        // past len_k as zeros (ragged k_len; kv_row0 = -1 with len_k < Lq)
+        const int rows = a.kv_row0 < 0 ? min(p.Lq, p.Lk) : p.Lk - a.kv_row0;
+        const size_t off = (size_t)b * a.dkv_bs + (size_t)h * a.dkv_hs + (size_t)(k_abs - row0) * a.dkv_rs;
+        bf16* dK = reinterpret_cast<bf16*>(a.dK) + off;
+        bf16* dV = reinterpret_cast<bf16*>(a.dV) + off;
+        if (!live && k_abs - row0 < rows) {
+            const bf16x4 z = {0, 0, 0, 0};
+#pragma unroll
+            for (int nt = 0; nt < NDT; ++nt) {
+                const int d = nt * 16 + g * 4;
+                if (d >= p.D) continue;
+                *reinterpret_cast<bf16x4*>(dK + d) = z;
+                *reinterpret_cast<bf16x4*>(dV + d) = z;
+            }
+        }
+        if (kt0 >= len_k) return;
         bf16x8 kf[NKK], vf[NKK];
 #pragma unroll
         for (int kk = 0; kk < NKK; ++kk) {
@@ -307,10 +326,7 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_kernel(AttnBwdArgs a) {
                 }
             }
         }
-        if (!live) return;
-        const size_t off = (size_t)b * a.dkv_bs + (size_t)h * a.dkv_hs + (size_t)(k_abs - row0) * a.dkv_rs;
-        bf16* dK = reinterpret_cast<bf16*>(a.dK) + off;
-        bf16* dV = reinterpret_cast<bf16*>(a.dV) + off;
+        if (!live) return;   // stored as zeros above
 #pragma unroll
         for (int nt = 0; nt < NDT; ++nt) {
             const int d = nt * 16 + g * 4;

@@ -362,7 +362,9 @@ def gemm_nn(x, w, out=None, out_dtype=torch.float32, splits: Optional[int] = Non
 def attention_bwd(q, k, v, o, do, scale=None, causal=False, k_len=None, kv_bdiv=1, dq=None, dk=None, dv=None, kv_row0=0, need_dkv=True,
                   nsplit: Optional[int] = None, drop_p: float = 0.0, drop_seed: int = 0, drop_salt=None):
     """backward of ops.attention (dense): q/o/do [B, Lq, H, D], k/v [Bk, Lk, Hkv, D] (last dim contiguous, other strides free).
-    Returns (dq [B,Lq,H,D], dk, dv [B, Lk - kv_row0, H, D]) - dk / dv are per QUERY head (sum GQA groups outside)."""
+    Returns (dq [B,Lq,H,D], dk, dv [B, Lk - kv_row0, H, D]) - dk / dv are per QUERY head (sum GQA groups outside).
+    kv_row0 = -1: the last Lq key rows of every sequence (keys max(0, k_len - Lq) ..), dk / dv [B, min(Lq, Lk), H, D].
+    dk / dv rows of keys at or past k_len are written as zero."""
     assert q.dtype == k.dtype == v.dtype == o.dtype == do.dtype == torch.bfloat16
     B, Lq, H, D = q.shape
     Bk, Lk, Hkv, _ = k.shape
@@ -400,11 +402,11 @@ def attention_bwd(q, k, v, o, do, scale=None, causal=False, k_len=None, kv_bdiv=
         nsplit = min(32, (Lk + 127) // 128) if (Lq <= 32 and Lk >= 512) else 1
     dq32 = None
     if nsplit > 1:
-        part = torch.empty(B, H, nsplit, 2, Lq, dtype=torch.float32, device=q.device)
+        part = torch.empty(B, H, (Lk + 63) // 64, 2, Lq, dtype=torch.float32, device=q.device)     # (m, l) of every 64-key block
         dq32 = torch.zeros(B, Lq, H, D, dtype=torch.float32, device=q.device)
         a.nsplit, a.part, a.dq32 = nsplit, part.data_ptr(), dq32.data_ptr()
     if need_dkv:
-        rows = min(Lq, Lk) if kv_row0 < 0 else Lk - kv_row0
+        rows = min(Lq, Lk) if kv_row0 < 0 else max(0, Lk - kv_row0)      # (a kv_row0 past Lk is the library's to refuse)
         if dk is None:
             dk = torch.empty(B, rows, H, D, dtype=torch.bfloat16, device=q.device)
         if dv is None:

@@ -5,6 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.attn_bwd_ref import _fmix32, _keep_mask  # noqa: F401  (the host replica of ina_hash; other suites import it from here)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -284,24 +286,6 @@ def test_attention_bwd_packed_views(dev):
     _, dq_ref, dk_ref, dv_ref = _attn_ref(q, k, v, do, D ** -0.5, False)
     for a, b in ((dq, dq_ref), (dk, dk_ref), (dv, dv_ref)):
         assert (a.float() - b).abs().max().item() < 2.5e-2 * b.abs().max().item()
-
-
-def _fmix32(h):
-    M = 0xFFFFFFFF
-    h = h ^ (h >> 16)
-    h = (h * 0x85EBCA6B) & M
-    h = h ^ (h >> 13)
-    h = (h * 0xC2B2AE35) & M
-    return h ^ (h >> 16)
-
-
-def _keep_mask(seed, idx, p):
-    """host replica of ina_hash (csrc/common.h) on int64 tensors: keep iff hash(seed, idx) >= p * 2^32."""
-    M = 0xFFFFFFFF
-    lo, hi = idx & M, idx >> 32
-    h = _fmix32((_fmix32(torch.full_like(lo, seed)) + 0x9E3779B9 * lo) & M)
-    h = _fmix32((h + 0x9E3779B9 * hi + 0x7F4A7C15) & M)
-    return h >= max(1, int(p * 4294967296.0))
 
 
 def test_dropout_mask_matches_host_replica(dev):
