@@ -400,6 +400,26 @@ typedef struct ina_argmax_args {
 } ina_argmax_args;
 int ina_argmax_rows(const ina_argmax_args* args, void* stream);
 
+/* ---- token_seen_set / argmax_penalty_rows: the repetition penalty of greedy decoding, what HF generate() applies on every greedy step when
+ *      the checkpoint's generation_config.json sets repetition_penalty (RepetitionPenaltyLogitsProcessor over prompt + answer so far).
+ *  A row's seen set is a bitmap: token t is bit t & 31 of word t >> 5 of seen[r] (uint32 [rows, ld_words], ld_words * 32 >= n).
+ *
+ *  token_seen_set: seen[r] becomes exactly the bitmap of { ids[r, i] : i < lens[r], 0 <= ids[r, i] < n } (ids int32 [rows, ld_ids], lens int32
+ *  [rows], at most ld_ids ids of a row are read). Bits left by an earlier call are cleared in the same launch; the bits of the last word
+ *  beyond n, the words at or beyond ceil(n / 32) and rows >= rows are left untouched. Ids outside [0, n) are ignored, never an out-of-bounds
+ *  access. One workgroup per row builds the bitmap in LDS (no global atomics): n <= 262144 (a 32 KiB LDS bitmap), a larger vocabulary is
+ *  refused.
+ *
+ *  argmax_penalty_rows: out[r] = argmax_j y[r, j] by the selection rule of argmax_rows (first maximum, NaN never selected, a row without an entry
+ *  above -inf gives 0, the result always in [0, n)), with y = x where the token's bit is clear and y = x < 0 ? x * penalty : x / penalty (fp32,
+ *  IEEE division: bit-equal to torch on the host) where it is set. X (f32 [rows, ldx]) is NOT modified. mark != 0: the chosen token's bit is
+ *  then set in seen[r] (the row's workgroup is its only writer), so decode steps chain without host work. penalty must be finite and > 0.
+ *  Refusals (null pointers, rows <= 0, n <= 0, ld_words * 32 < n, bad penalty) return non-zero before any HIP call.
+ *  Plain arguments: no struct, no ABI bump. */
+int ina_token_seen_set(uint32_t* seen, int32_t ld_words, const int32_t* ids, int32_t ld_ids, const int32_t* lens, int32_t rows, int32_t n, void* stream);
+int ina_argmax_penalty_rows(const float* X, int32_t ldx, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
+                            int32_t* out, void* stream);
+
 /* ---- select_traj: per env, rank the S samples by critic value; neg = the k lowest (ascending), pos = the k highest
  *      (descending); trajectories are cumsum_t(sample * scale).  reference: navdp_policy.py:317-320. */
 typedef struct ina_select_args {

@@ -86,7 +86,8 @@ class InternVLAN1Agent:
         `policy = get_policy(policy_name)(config=get_config(policy_name)(model_cfg={'model': model_settings}))`, which loads the
         checkpoint at model_settings['model_path'] on model_settings['device'] and the HF processor from the same path.
         model_settings read: model_path, device, policy_name, infer_mode ('sync' | 'partial_async'), sys2_max_forward_step, num_history,
-        resize_w/h, width/height (camera), continuous_traj, env_num (engine capacity), device_preprocess (optional), device_actions
+        resize_w/h, width/height (camera), continuous_traj, env_num (engine capacity), repetition_penalty (optional: overrides the
+        checkpoint's generation_config.json), ignore_generation_config (optional), device_preprocess (optional), device_actions
         (optional, default False: System-1's trajectories become the step's action table in one kernel launch instead of one numpy
         traj_to_actions per env; `last_action_table` then holds the int32 [n, 4] table of the last System-1 call on the device).
         Tests / bench may pass a built `model` + `processor`, or a `policy_factory() -> InternVLAN1Net`, instead."""
@@ -106,7 +107,8 @@ class InternVLAN1Agent:
                 assert processor is not None, "a pre-built model needs its processor"
                 first = InternVLAN1Net(model, processor, num_history=ms.get("num_history", 8), resize_w=ms.get("resize_w", 384),
                                        resize_h=ms.get("resize_h", 384), continuous_traj=ms.get("continuous_traj", True),
-                                       frame_preprocessor=frame_preprocessor, kv_reuse=ms.get("kv_reuse", False))
+                                       frame_preprocessor=frame_preprocessor, kv_reuse=ms.get("kv_reuse", False),
+                                       repetition_penalty=ms.get("repetition_penalty"))
             else:
                 from . import get_config, get_policy
 
@@ -279,6 +281,11 @@ class InternVLAN1Agent:
                     if any(kv is not None or want for kv, want in pref):
                         gen_extra.update(prefix_kv=[kv for kv, _ in pref], export_prefix=[want for _, want in pref])
                     pkv = [past.get(id(it)) for it in items]
+                    pens = {getattr(it[0].policy, "repetition_penalty", None) for it in items}    # model_settings['repetition_penalty'], as s2_step passes it
+                    assert len(pens) == 1, f"the envs of one System-2 batch carry different repetition penalties: {pens}"
+                    pen = pens.pop()
+                    if pen is not None:
+                        gen_extra["repetition_penalty"] = float(pen)
                     res = model.generate(input_ids=ids, pixel_values=pv, image_grid_thw=grid, max_new_tokens=128, do_sample=False, use_cache=True,
                                          past_key_values=pkv if any(c is not None for c in pkv) else None, return_dict_in_generate=True,
                                          **ragged, **gen_extra)

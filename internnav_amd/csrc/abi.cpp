@@ -193,6 +193,15 @@ int ina_traj_actions(void* traj, int32_t traj_dtype, int32_t B, int32_t S, int32
     return ina_launch_traj_actions(traj, traj_dtype, B, S, T, actions, max_actions, count, traj_out, scale_in_place, reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_token_seen_set(uint32_t* seen, int32_t ld_words, const int32_t* ids, int32_t ld_ids, const int32_t* lens, int32_t rows, int32_t n, void* stream) {
+    return ina_launch_token_seen_set(seen, ld_words, ids, ld_ids, lens, rows, n, reinterpret_cast<hipStream_t>(stream));
+}
+
+int ina_argmax_penalty_rows(const float* X, int32_t ldx, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
+                            int32_t* out, void* stream) {
+    return ina_launch_argmax_penalty(X, ldx, rows, n, seen, ld_words, penalty, mark, out, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_gemm_select(const ina_gemm_args* args, int* kernel) {
     INA_REQUIRE(args != nullptr && kernel != nullptr, "gemm_select: null argument");
     GemmArgs p;

@@ -70,6 +70,10 @@ int ina_launch_memory_gather(void* out, long out_env_stride, float* ring, const 
                              int stride, hipStream_t stream);                                                                // memory_gather.hip
 int ina_launch_traj_actions(void* traj, int traj_dtype, int B, int S, int T, int32_t* actions, int max_actions, int32_t* count, double* traj_out,
                             int scale_in_place, hipStream_t stream);                                                         // traj_actions.hip
+int ina_launch_token_seen_set(uint32_t* seen, int ld_words, const int32_t* ids, int ld_ids, const int32_t* lens, int rows, int n,
+                              hipStream_t stream);                                                                           // decode_penalty.hip
+int ina_launch_argmax_penalty(const float* X, int ldx, int rows, int n, uint32_t* seen, int ld_words, float penalty, int mark, int32_t* out,
+                              hipStream_t stream);                                                                           // decode_penalty.hip
 int ina_launch_head3(const Head3Args& p, hipStream_t stream);
 int ina_launch_seqpool(const SeqpoolArgs& p, hipStream_t stream);
 int ina_launch_select(const SelectArgs& p, hipStream_t stream);

@@ -618,6 +618,28 @@ def argmax_rows(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def token_seen_set(seen: torch.Tensor, ids: torch.Tensor, lens: torch.Tensor, n: int) -> torch.Tensor:
+    """seen[r] (uint32 [rows, ld_words], token t = bit t & 31 of word t >> 5) = the set of ids[r, :lens[r]] inside [0, n):
+    the tokens a repetition penalty acts on. Stale bits are cleared in the same launch; ids int32 [rows, ld_ids], lens int32 [rows]."""
+    assert seen.dtype in (torch.uint32, torch.int32) and seen.dim() == 2 and seen.stride(1) == 1 and ids.dtype == torch.int32 and ids.dim() == 2 and ids.stride(1) == 1
+    rows = ids.shape[0]
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == rows and seen.shape[0] >= rows and seen.shape[1] * 32 >= n
+    rc = _lib.lib().ina_token_seen_set(seen.data_ptr(), seen.stride(0), ids.data_ptr(), ids.stride(0), lens.data_ptr(), rows, int(n), _stream())
+    _lib.check(rc, "token_seen_set")
+    return seen
+
+
+def argmax_penalty_rows(x: torch.Tensor, seen: torch.Tensor, penalty: float, out: torch.Tensor, mark: bool = True) -> torch.Tensor:
+    """out[r] = argmax_rows of the repetition-penalised f32 row r (HF RepetitionPenaltyLogitsProcessor: a seen token's logit is divided by the
+    penalty when >= 0, multiplied when < 0); x is not modified. mark: the chosen token's bit is set in seen[r] by the same launch."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and out.dtype == torch.int32 and out.numel() == x.shape[0]
+    assert seen.dtype in (torch.uint32, torch.int32) and seen.dim() == 2 and seen.stride(1) == 1 and seen.shape[0] >= x.shape[0] and seen.shape[1] * 32 >= x.shape[1]
+    rc = _lib.lib().ina_argmax_penalty_rows(x.data_ptr(), x.stride(0), x.shape[0], x.shape[1], seen.data_ptr(), seen.stride(0), float(penalty),
+                                            int(bool(mark)), out.data_ptr(), _stream())
+    _lib.check(rc, "argmax_penalty_rows")
+    return out
+
+
 def dit_v2t(kv2: torch.Tensor, heads: int, v2t: torch.Tensor) -> torch.Tensor:
     """condition V of a NextDiT block -> the transposed key-permuted image dit_attention consumes.
     kv2 bf16 [envs, Lz, 2, heads, 64] (K | V as produced by the fused kv projection); v2t bf16 [envs, heads, 64, 64]."""

@@ -31,7 +31,7 @@ import torch
 from . import synthetic
 from .navdp import NavDPPolicyDAT
 from .nextdit import NextDiTSystem1
-from .qwen_vl import ATTN_WIDE_MIN_ROWS, SKINNY_GEMM_MAX_ROWS, EngineKVCache, QwenVLEngine, kv_reuse_fit, kv_reuse_lengths
+from .qwen_vl import ATTN_WIDE_MIN_ROWS, SKINNY_GEMM_MAX_ROWS, EngineKVCache, QwenVLEngine, eos_ids, kv_reuse_fit, kv_reuse_lengths
 from .runtime import CapacityError  # noqa: F401  (re-exported)
 
 
@@ -182,16 +182,49 @@ def qwen_cfg_from_hf(cfgj: dict) -> dict:
         eos_token_id=int(eos[0] if isinstance(eos, (list, tuple)) else eos))
 
 
+# generation_config.json keys that change what greedy generate() returns and that the engine does not implement -> the value that leaves
+# HF's behaviour unchanged (a key set to anything else is refused at load: never differ silently)
+_GEN_REFUSED = {
+    "no_repeat_ngram_size": lambda v: not v or v <= 0, "encoder_repetition_penalty": lambda v: v is None or float(v) == 1.0,
+    "bad_words_ids": lambda v: not v, "suppress_tokens": lambda v: not v, "begin_suppress_tokens": lambda v: not v,
+    "forced_bos_token_id": lambda v: v is None, "forced_eos_token_id": lambda v: v is None, "min_length": lambda v: not v or v <= 0,
+    "min_new_tokens": lambda v: not v or v <= 0, "sequence_bias": lambda v: not v, "num_beams": lambda v: v is None or v <= 1,
+    "penalty_alpha": lambda v: v is None, "exponential_decay_length_penalty": lambda v: v is None, "renormalize_logits": lambda v: not v}
+
+
+def generation_config_from_hf(raw: Optional[dict], default_eos, ignore: bool = False) -> SimpleNamespace:
+    """what `generate(do_sample=False)` honours of a checkpoint's generation_config.json (HF starts from that file and overrides only the
+    keys it is passed): `repetition_penalty` (default 1.0) and `eos_token_id` (an int or a list; default: config.json's) -> a namespace with
+    repetition_penalty, eos_token_id (tuple) and the raw dict. raw None = no file: penalty 1.0, EOS of config.json.
+    Sampling-only keys (do_sample, temperature, top_k, top_p, min_p, typical_p) are ignored, as HF ignores them under do_sample=False.
+    A key that changes greedy output and is not implemented raises NotImplementedError naming it, unless `ignore`."""
+    raw = dict(raw or {})
+    bad = sorted(k for k, ok in _GEN_REFUSED.items() if k in raw and not ok(raw[k]))
+    if bad and not ignore:
+        raise NotImplementedError(
+            f"generation_config.json sets {', '.join(f'{k}={raw[k]!r}' for k in bad)}: greedy decoding with these is not implemented, and ignoring "
+            "them would decode other tokens than transformers does (model_settings['ignore_generation_config']=True loads anyway)")
+    pen = raw.get("repetition_penalty")
+    pen = 1.0 if pen is None else float(pen)
+    if not (np.isfinite(pen) and pen > 0.0):
+        raise ValueError(f"generation_config.json: repetition_penalty={raw.get('repetition_penalty')!r} is not a strictly positive float")
+    eos = raw.get("eos_token_id")
+    return SimpleNamespace(repetition_penalty=pen, eos_token_id=eos_ids(default_eos if eos is None else eos), raw=raw)
+
+
 class InternVLAN1ForCausalLM:
     """HF-style model object backed by the HIP engines (no nn.Module, no CPU fallback)."""
 
     def __init__(self, weights, qwen_cfg: dict, system1: str = "nextdit_async", s1_cfg: Optional[dict] = None,
                  device="cuda:0", max_envs: int = 16, max_seq_len: Optional[int] = None, max_patches: Optional[int] = None,
                  max_s2_seqs: Optional[int] = None, num_history: int = 8, resize_w: int = 384, resize_h: int = 384,
-                 cam_w: int = 640, cam_h: int = 480, w8_decode: bool = False):
+                 cam_w: int = 640, cam_h: int = 480, w8_decode: bool = False, generation_config: Optional[dict] = None,
+                 ignore_generation_config: bool = False):
         """Engine capacity defaults to the longest prompt the reference's harness can build for (num_history, resize, camera size):
         see `s2_capacity`; exceeding it raises `CapacityError` (never a silent STOP)."""
         self.device = torch.device(device)
+        # the checkpoint's generation_config.json (None: no such file): generate() starts from it, as HF's does
+        self.generation_config = generation_config_from_hf(generation_config, qwen_cfg["eos_token_id"], ignore=ignore_generation_config)
         if system1 not in ("nextdit_async", "navdp_async", "nextdit", "navdp"):
             # the four System-1 types of generate_traj (internvla_n1.py:359-441): 'nextdit' [+ 'async'] and 'navdp' [+ 'async']
             raise NotImplementedError(f"system1={system1!r}: known types are 'nextdit_async' (DualVLN), 'navdp_async', 'nextdit', 'navdp'")
@@ -219,7 +252,10 @@ class InternVLAN1ForCausalLM:
     def from_pretrained(cls, path, torch_dtype=torch.bfloat16, attn_implementation: str = "flash_attention_2", device_map=None, **kw):
         """reference call: InternVLAN1ForCausalLM.from_pretrained(path, torch_dtype=bf16, attn_implementation=..., device_map={"": dev}).
         Loads every *.safetensors shard under `path` (HF checkpoint layout, the reference's parameter names); config.json supplies the
-        Qwen2.5-VL dimensions / token ids, system1 and n_query (InternVLAN1ModelConfig fields, internvla_n1.py:22-29)."""
+        Qwen2.5-VL dimensions / token ids, system1 and n_query (InternVLAN1ModelConfig fields, internvla_n1.py:22-29);
+        generation_config.json, when present, supplies repetition_penalty and eos_token_id of generate() (`model.generation_config`,
+        `generation_config_from_hf`: unimplemented keys that change greedy output raise NotImplementedError unless
+        ignore_generation_config=True is passed)."""
         import json
         from pathlib import Path
 
@@ -231,6 +267,9 @@ class InternVLAN1ForCausalLM:
             raise FileNotFoundError(f"no *.safetensors under {p}: InternVLA-N1 checkpoints are HF safetensors shards")
         cfgj = json.loads((p / "config.json").read_text()) if (p / "config.json").exists() else {}
         device = (device_map or {"": "cuda:0"})[""]
+        genj = json.loads((p / "generation_config.json").read_text()) if (p / "generation_config.json").exists() else None
+        # only the refusal check, before any weight is read (the EOS default is a placeholder): __init__ builds the namespace the model keeps
+        generation_config_from_hf(genj, 0, ignore=bool(kw.get("ignore_generation_config", False)))
         weights = _ShardedCheckpoint(files)
         system1 = cfgj.get("system1", "nextdit_async")
         s1_cfg = None
@@ -246,7 +285,7 @@ class InternVLAN1ForCausalLM:
         bad = [(k, weights.shape_of(k), shp) for k, (shp, _) in spec.items() if k.startswith("model.traj_dit.") and tuple(weights.shape_of(k)) != tuple(shp)]
         if bad:
             raise ValueError(f"checkpoint {p}: {len(bad)} NextDiT tensors do not have the shapes its own geometry implies, e.g. {bad[:3]}")
-        return cls(weights, qwen_cfg_from_hf(cfgj), system1=system1, s1_cfg=s1_cfg, device=device, **kw)
+        return cls(weights, qwen_cfg_from_hf(cfgj), system1=system1, s1_cfg=s1_cfg, device=device, generation_config=genj, **kw)
 
     def eval(self):
         return self
@@ -261,9 +300,13 @@ class InternVLAN1ForCausalLM:
     def generate(self, input_ids=None, pixel_values=None, image_grid_thw=None, attention_mask=None, max_new_tokens: int = 128,
                  do_sample: bool = False, use_cache: bool = True, past_key_values=None, return_dict_in_generate: bool = False,
                  decode_chunk: int = 8, eos_token_id=None, cached_image_embeds: Optional[list] = None, prefix_kv: Optional[list] = None,
-                 export_prefix: Optional[list] = None, **_):
+                 export_prefix: Optional[list] = None, repetition_penalty: Optional[float] = None, **_):
         """greedy decoding (do_sample=False is the only mode the reference uses, internvla_n1_policy.py:169-176). Decodes in chunks of
         `decode_chunk` device-side steps and stops once every sequence has emitted EOS. Sequences are right-filled with EOS.
+        repetition_penalty / eos_token_id: None = the checkpoint's generation_config.json (`self.generation_config`; without that file 1.0
+        and config.json's EOS), an explicit value overrides it as HF kwargs do. The penalty acts on every greedy step over prompt + answer
+        so far (HF RepetitionPenaltyLogitsProcessor; for a ragged batch over each row's real tokens); eos_token_id may be a list, any
+        member ends a row and rows are right-filled with the first.
         cached_image_embeds (extension, per-frame ViT cache): one entry per image of the batch, None = encode it (its patches are in
         pixel_values), else the embeddings an earlier call returned through `last_image_embeds()`.
         prefix_kv (extension, prefix-KV reuse): one entry per sequence - None, or the K/V bf16 [layers, P, 1024] of the sequence's first P
@@ -278,7 +321,9 @@ class InternVLAN1ForCausalLM:
         With return_dict_in_generate and use_cache the result carries `.past_key_values`: an EngineKVCache of every sequence's PROMPT
         rows (not the answer: see EngineKVCache)."""
         assert not do_sample, "the reference only decodes greedily"
-        eos = self.qwen.cfg["eos_token_id"] if eos_token_id is None else eos_token_id
+        eos_all = self.generation_config.eos_token_id if eos_token_id is None else eos_ids(eos_token_id)
+        eos, eos_t = eos_all[0], torch.tensor(eos_all, dtype=torch.long)
+        penalty = self.generation_config.repetition_penalty if repetition_penalty is None else float(repetition_penalty)
         pv = pixel_values.to(self.device, torch.bfloat16) if pixel_values is not None and pixel_values.numel() else None
         B, S = input_ids.shape
         # ragged batch (extension; the reference is batch 1): prompts RIGHT-padded to a common length, real lengths from attention_mask
@@ -311,7 +356,7 @@ class InternVLAN1ForCausalLM:
                 keep = [pv[off[i]:off[i + 1]] for i, s in enumerate(skip) if not s]
                 pv = torch.cat(keep, 0) if keep else None
         state = self.qwen.prefill(input_ids, pv, image_grid_thw, cached_embeds=cached_image_embeds, seq_lens=plens if attention_mask is not None else None,
-                                  prefix_len=pl)
+                                  prefix_len=pl, **({} if penalty == 1.0 else {"repetition_penalty": penalty}))
         self._prefix_out = {}
         if export_prefix is not None:
             for b, n in enumerate(export_prefix):
@@ -325,12 +370,12 @@ class InternVLAN1ForCausalLM:
             t = t[:, 1:] if n else t
             chunks.append(t.cpu().long())
             n += k
-            if bool((torch.cat(chunks, dim=1) == eos).any(dim=1).all()):
+            if bool(torch.isin(torch.cat(chunks, dim=1), eos_t).any(dim=1).all()):
                 break
         toks = torch.cat(chunks, dim=1)
         lens = []
         for b in range(toks.shape[0]):
-            hit = (toks[b] == eos).nonzero()
+            hit = torch.isin(toks[b], eos_t).nonzero()
             e = int(hit[0]) + 1 if hit.numel() else toks.shape[1]
             toks[b, e:] = eos
             lens.append(e)
@@ -521,7 +566,7 @@ class InternVLAN1Net:
 
     def __init__(self, config=None, processor=None, num_history: int = 8, resize_w: int = 384, resize_h: int = 384,
                  continuous_traj: bool = True, frame_preprocessor=None, model: Optional[InternVLAN1ForCausalLM] = None,
-                 vit_cache: bool = False, prefix_cache: bool = False, kv_reuse: bool = False):
+                 vit_cache: bool = False, prefix_cache: bool = False, kv_reuse: bool = False, repetition_penalty: Optional[float] = None):
         """Two ways in, both ending in (model, processor, episode state):
           * the reference's: `InternVLAN1Net(config=InternVLAN1ModelConfig(model_cfg={'model': model_settings}))`
             (internvla_n1_agent.py:39-43, internvla_n1_policy.py:29-48) - loads the checkpoint at model_settings['model_path'] on
@@ -560,6 +605,9 @@ class InternVLAN1Net:
             and hasattr(getattr(model, "qwen", None), "kv_handle")
         self.prefix_cache = bool(prefix_cache or (config is not None and dict(config.model_cfg["model"]).get("prefix_cache", False))) \
             and hasattr(getattr(model, "qwen", None), "export_prefix_kv") and not self.vit_cache and not self.kv_reuse
+        # model_settings['repetition_penalty'] (None: the checkpoint's generation_config.json): passed to every System-2 generate() of this env,
+        # by s2_step and by the batched agent alike
+        self.repetition_penalty = dict(config.model_cfg["model"]).get("repetition_penalty", repetition_penalty) if config is not None else repetition_penalty
         self.tokenizer = getattr(processor, "tokenizer", None)
         self.num_history, self.resize_w, self.resize_h, self.continuous_traj = num_history, resize_w, resize_h, continuous_traj
         self.device = model.device
@@ -568,14 +616,15 @@ class InternVLAN1Net:
     @classmethod
     def _load(cls, ms: dict):
         """model + processor for a model_settings dict, loaded once per (checkpoint, device) and shared afterwards."""
-        key = (str(ms["model_path"]), str(ms.get("device", "cuda:0")), bool(ms.get("w8_decode", False)))
+        key = (str(ms["model_path"]), str(ms.get("device", "cuda:0")), bool(ms.get("w8_decode", False)), bool(ms.get("ignore_generation_config", False)))
         if key not in cls._shared:
             n_env = int(ms.get("env_num", 1) or 1)
             model = InternVLAN1ForCausalLM.from_pretrained(
                 ms["model_path"], torch_dtype=torch.bfloat16, attn_implementation="flash_attention_2", device_map={"": ms.get("device", "cuda:0")},
                 max_envs=max(n_env, int(ms.get("max_envs", 1))), max_s2_seqs=ms.get("max_s2_seqs"), num_history=ms.get("num_history", 8),
                 resize_w=ms.get("resize_w", 384), resize_h=ms.get("resize_h", 384), cam_w=ms.get("width", 640), cam_h=ms.get("height", 480),
-                w8_decode=bool(ms.get("w8_decode", False)))      # System-2 single-token passes on FP8 weights (QwenVLEngine(w8_decode=True))
+                w8_decode=bool(ms.get("w8_decode", False)),      # System-2 single-token passes on FP8 weights (QwenVLEngine(w8_decode=True))
+                ignore_generation_config=bool(ms.get("ignore_generation_config", False)))
             cls._shared[key] = (model.eval(), cls.load_processor(ms["model_path"]))
         return cls._shared[key]
 
@@ -594,7 +643,7 @@ class InternVLAN1Net:
         """a fresh episode state on the same model / processor (the batched agent keeps one per environment)."""
         return InternVLAN1Net(processor=self.processor, num_history=self.num_history, resize_w=self.resize_w, resize_h=self.resize_h,
                               continuous_traj=self.continuous_traj, frame_preprocessor=self.pre, model=self.model, vit_cache=self.vit_cache,
-                              prefix_cache=self.prefix_cache, kv_reuse=self.kv_reuse)
+                              prefix_cache=self.prefix_cache, kv_reuse=self.kv_reuse, repetition_penalty=self.repetition_penalty)
 
     def eval(self):
         return self
@@ -781,6 +830,8 @@ class InternVLAN1Net:
         if self.kv_reuse:
             past, self._kv = self.kv_request(inputs), None    # dropped until this call succeeds (S2 failure / retry path)
             past = [past] if past is not None else None
+        if self.repetition_penalty is not None:
+            extra["repetition_penalty"] = float(self.repetition_penalty)
         res = self.model.generate(input_ids=inputs["input_ids"], pixel_values=inputs["pixel_values"], image_grid_thw=inputs["image_grid_thw"],
                                   max_new_tokens=128, do_sample=False, use_cache=True, past_key_values=past, return_dict_in_generate=True, **extra)
         ids = res.sequences

@@ -153,6 +153,13 @@ def kv_reuse_fit(pl: np.ndarray, S: int, tail: int, s_max: int) -> Tuple[np.ndar
     return pl, dropped
 
 
+def eos_ids(eos) -> Tuple[int, ...]:
+    """eos_token_id as HF takes it - an int or a list of ints, any of which ends a row - as a non-empty tuple"""
+    out = tuple(int(e) for e in (eos if isinstance(eos, (list, tuple)) else [eos]))
+    assert out, "eos_token_id: an int or a non-empty list"
+    return out
+
+
 class EngineKVCache:
     """K/V of the PROMPT rows of each sequence of a System-2 call, per row bf16 [layers, n_b, kv_w] with the token ids (int64, CPU) they
     cover: what `generate(return_dict_in_generate=True, use_cache=True).past_key_values` returns and `generate(past_key_values=...)`
@@ -364,6 +371,9 @@ class QwenVLEngine:
         self.xl = torch.empty(max_seqs, H, dtype=f32, device=dev)
         self.logits = torch.empty(max_seqs, cfg["vocab"], dtype=f32, device=dev)
         self.next_tok = torch.empty(max_seqs, dtype=torch.int32, device=dev)
+        # repetition penalty (generation_config.json, HF RepetitionPenaltyLogitsProcessor): per sequence the bitmap of the tokens seen so far
+        # (token t = bit t & 31 of word t >> 5; rows of a multiple of 4 words). Only a call with a penalty != 1 ever touches it.
+        self.seen = torch.zeros(max_seqs, ((cfg["vocab"] + 31) // 32 + 3) // 4 * 4, dtype=torch.uint32, device=dev)
         half = self.hd // 2
         self.inv_freq = (1.0 / (cfg["rope_theta"] ** (torch.arange(0, self.hd, 2, dtype=f32) / self.hd))).to(dev)
         axis = np.concatenate([np.full(16, 0), np.full(24, 1), np.full(24, 2)]).astype(np.int32)  # mrope_section [16, 24, 24]
@@ -377,7 +387,7 @@ class QwenVLEngine:
         self._kv_base = None                                     # int64 [layers] device table of the layers' cache addresses (ina_kv_copy)
 
     _BUFFERS = ("pv_perm", "xv", "hv", "attv", "qkvv", "ffv", "mh", "emb", "emb_tok", "v_cos", "v_sin", "x_in", "x", "h", "att", "qkv", "ff", "cos", "sin",
-                "hl", "xl", "logits", "next_tok")
+                "hl", "xl", "logits", "next_tok", "seen")
 
     def twin(self) -> "QwenVLEngine":
         """a second engine over the SAME weight tensors (nothing is copied; `latent_q` stays one shared parameter) with its own activation
@@ -558,9 +568,10 @@ class QwenVLEngine:
             if self.tap is not None:
                 self.tap("llm", li, x)
 
-    def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None):
+    def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None, penalty: Optional[float] = None):
         """final RMSNorm + lm_head on ONE row per sequence, greedy argmax on the device. row_in_seq: the same row for every sequence,
-        or (ragged batches) rows_idx int32 [B] = absolute row of each sequence's last real token."""
+        or (ragged batches) rows_idx int32 [B] = absolute row of each sequence's last real token. penalty: the selection runs over the
+        repetition-penalised logits of the tokens in `seen` and marks the chosen one (`logits` keeps the raw values)."""
         if rows_idx is not None:
             ops.gather_rows(self.x[: B * S], self.xl[:B], src=rows_idx)
             ops.norm(self.xl[:B], self.norm_w, None, eps=1e-6, rms=True, out=self.hl[:B], rows=B)
@@ -570,11 +581,18 @@ class QwenVLEngine:
             ops.linear_w8(self.hl[:B], *self.lm_head8, out=self.logits[:B])
         else:
             ops.linear(self.hl[:B], self.lm_head, out=self.logits[:B])     # (152064 columns: one wave per 16-column tile owns all of K)
-        ops.argmax_rows(self.logits[:B], self.next_tok[:B])
+        if penalty is None:
+            ops.argmax_rows(self.logits[:B], self.next_tok[:B])
+        else:
+            ops.argmax_penalty_rows(self.logits[:B], self.seen, penalty, self.next_tok[:B], mark=True)
+
+    def _seen_init(self, P: dict):
+        """launch in front of a decode's first selection: every sequence's seen set = its whole prompt (cached prefix included)"""
+        ops.token_seen_set(self.seen, P["rep_ids"], P["rep_lens"], self.cfg["vocab"])
 
     # ---- plan / run: all host work up front, then a pure launch sequence (hipGraph capturable)
     def plan(self, input_ids, image_grid_thw, n_decode: int = 0, with_latents: bool = False, cached_embeds: Optional[list] = None,
-             prefix_len=0) -> dict:
+             prefix_len=0, repetition_penalty: float = 1.0, seq_lens=None) -> dict:
         """Host-side plan of one S2 call for B equal-length prompts: embedding / scatter indices, vision plan, position ids and cache
         rows of the prefill, of every decode step and of the latent-query pass (fixed-length answers of n_decode tokens).
         cached_embeds: one entry per image (prompt order over the batch), None = run the vision tower on it, else its merged embeddings
@@ -586,8 +604,15 @@ class QwenVLEngine:
         the K/V of a token depend on the tokens before it only, so the suffix sees exactly what a full prefill would have cached.
         Images whose tokens lie inside the prefix are not encoded (pixel_values holds the patches of the other images); the prefix
         must end on an image boundary. prefix_len may be an int or one value per sequence (0 = nothing cached for that sequence): the
-        call then runs a right-padded rectangle of max(S - prefix_len) tokens per sequence behind each sequence's own prefix."""
+        call then runs a right-padded rectangle of max(S - prefix_len) tokens per sequence behind each sequence's own prefix.
+        repetition_penalty (generation_config.json; HF RepetitionPenaltyLogitsProcessor): != 1.0 makes every greedy selection of the decode
+        run over the penalised logits of the tokens seen so far - the WHOLE prompt (image placeholders and tokens whose K/V came from a
+        cache included; seq_lens [B] real tokens of right-padded prompts) plus the answer. The plan then uploads the full ids [B, S] and the
+        lengths; with 1.0 nothing is uploaded and the launch sequence is the plain one."""
         cfg, dev = self.cfg, self.device
+        pen = float(repetition_penalty)
+        if not (np.isfinite(pen) and pen > 0.0):
+            raise ValueError(f"repetition_penalty={repetition_penalty!r}: HF requires a strictly positive float")
         ids = (input_ids.cpu().numpy() if isinstance(input_ids, torch.Tensor) else np.asarray(input_ids)).astype(np.int64)
         B, S = ids.shape
         if B > self.B_max or S > self.S_max:
@@ -608,6 +633,12 @@ class QwenVLEngine:
         prefix_len = pl
         P = dict(B=B, S=S, S_run=Sr, prefix_len=prefix_len, n_decode=n_decode, ids=torch.from_numpy(flat.astype(np.int32)).to(dev), vision=None,
                  cached=[], fresh_tokens=[])
+        if pen != 1.0:
+            lens = np.full(B, S, dtype=np.int64) if seq_lens is None else np.asarray(seq_lens, dtype=np.int64).reshape(B)
+            assert int(lens.min()) >= 1 and int(lens.max()) <= S
+            P["rep_penalty"] = pen
+            P["rep_ids"] = torch.from_numpy(ids.astype(np.int32)).to(dev)
+            P["rep_lens"] = torch.from_numpy(lens.astype(np.int32)).to(dev)
         img_pos = np.nonzero(flat == cfg["image_token_id"])[0].astype(np.int32)
         if grids:
             ntok_all = [t * h * w // 4 for t, h, w in grids]
@@ -750,15 +781,18 @@ class QwenVLEngine:
         j1 = n if j1 is None else min(j1, n)
         if n == 0 or j0 >= j1:
             return
+        pen = P.get("rep_penalty")
         if j0 == 0:
-            self._last_logits(B, S, S - 1)
+            if pen is not None:
+                self._seen_init(P)                                # part of the launch sequence: a captured decode re-initialises the set on replay
+            self._last_logits(B, S, S - 1, penalty=pen)
         for j in range(j0, j1):
             tokens_out[:, j].copy_(self.next_tok[:B])
             if j == n - 1:
                 break
             ops.gather_rows(self.embed, self.x_in, src=self.next_tok[:B], rows=B)
             self._layers(P["decode"][j])
-            self._last_logits(B, 1, 0)
+            self._last_logits(B, 1, 0, penalty=pen)
 
     def run_latents(self, P: dict, out: torch.Tensor):
         """N_QUERY latent queries (behind the last sampled token) against the KV cache -> out bf16 [B, N_QUERY, H]."""
@@ -898,12 +932,13 @@ class QwenVLEngine:
 
     # ---- eager, stateful API (used by the policy layer: answers have data-dependent lengths)
     def prefill(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor], image_grid_thw, cached_embeds: Optional[list] = None,
-                seq_lens=None, prefix_len: int = 0) -> dict:
+                seq_lens=None, prefix_len: int = 0, repetition_penalty: float = 1.0) -> dict:
         """seq_lens [B] (optional): RAGGED batch - input_ids is right-padded to a common length S and sequence b has seq_lens[b] real
         tokens. Causal attention keeps every real position independent of the padding behind it, so the prefill runs on the padded
         rectangle; the first token is read at each sequence's own last position and the decode / latent passes append at per-sequence
         cache positions with per-sequence key lengths (the pad rows' K/V are never attended and get overwritten)."""
-        P = self.plan(input_ids, image_grid_thw, cached_embeds=cached_embeds, prefix_len=prefix_len)
+        P = self.plan(input_ids, image_grid_thw, cached_embeds=cached_embeds, prefix_len=prefix_len, repetition_penalty=repetition_penalty,
+                      seq_lens=seq_lens)
         self.run_prefill(P, pixel_values)
         return self.prefill_state(P, input_ids, image_grid_thw, seq_lens)
 
@@ -931,17 +966,20 @@ class QwenVLEngine:
         Sr = state.get("S_run", S)                                # rows per sequence in x (prompt minus a cached prefix)
         out = torch.empty(B, n_steps, dtype=torch.int32, device=self.device)
         lens = state.get("lens")
+        pen = state["plan"].get("rep_penalty")
         if "cur" not in state:
+            if pen is not None:
+                self._seen_init(state["plan"])
             if lens is None and bool((state["plan"]["prefix_len"] == state["plan"]["prefix_len"][0]).all()):
-                self._last_logits(B, Sr, Sr - 1)
+                self._last_logits(B, Sr, Sr - 1, penalty=pen)
                 state["cur"] = S
             elif lens is None:       # equal-length prompts behind prefixes of different lengths: each sequence's last real row
                 rows = torch.from_numpy((np.arange(B) * Sr + S - state["plan"]["prefix_len"] - 1).astype(np.int32)).to(self.device)
-                self._last_logits(B, Sr, None, rows_idx=rows)
+                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen)
                 state["cur"] = S
             else:
                 rows = torch.from_numpy((np.arange(B) * Sr + lens - state["plan"]["prefix_len"] - 1).astype(np.int32)).to(self.device)
-                self._last_logits(B, Sr, None, rows_idx=rows)
+                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen)
                 state["cur"] = lens.copy()
         for j in range(n_steps):
             out[:, j].copy_(self.next_tok[:B])
@@ -953,7 +991,7 @@ class QwenVLEngine:
                 self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur))
             else:
                 self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur, k_len=cur + 1))
-            self._last_logits(B, 1, 0)
+            self._last_logits(B, 1, 0, penalty=pen)
             state["cur"] = cur + 1
             state["next_pos"] = state["next_pos"] + 1
         return out
@@ -990,13 +1028,16 @@ class QwenVLEngine:
         return out
 
     # ------------------------------------------------------------------------------------------------ HF-style surface
-    def generate(self, input_ids, pixel_values=None, image_grid_thw=None, max_new_tokens: int = 8, eos_token_id=None, **_):
-        """greedy generate: returns sequences int64 [B, S + n] (a row that reached EOS keeps EOS), n = max_new_tokens."""
-        state = self.prefill(input_ids, pixel_values, image_grid_thw)
+    def generate(self, input_ids, pixel_values=None, image_grid_thw=None, max_new_tokens: int = 8, eos_token_id=None,
+                 repetition_penalty: float = 1.0, **_):
+        """greedy generate: returns sequences int64 [B, S + n] (a row that reached EOS keeps EOS), n = max_new_tokens.
+        eos_token_id: an int or a list (any member ends a row; the row is filled with the first); repetition_penalty as in `plan`."""
+        state = self.prefill(input_ids, pixel_values, image_grid_thw, repetition_penalty=repetition_penalty)
         toks = self.decode(state, max_new_tokens).cpu().long()
-        eos = self.cfg["eos_token_id"] if eos_token_id is None else eos_token_id
+        eos_all = eos_ids(self.cfg["eos_token_id"] if eos_token_id is None else eos_token_id)
+        eos = eos_all[0]
         for b in range(toks.shape[0]):
-            hit = (toks[b] == eos).nonzero()
+            hit = torch.isin(toks[b], torch.tensor(eos_all)).nonzero()
             if hit.numel():
                 toks[b, int(hit[0]) + 1:] = eos
         self._state = state

@@ -643,10 +643,11 @@ def n1_navdp_inputs(B: int, seed: int = 0, cfg=N1_NAVDP_CFG):
     return dict(vlm_tokens=vlm, images=images, depths=depths, x_init=x_init, step_noise=step_noise)
 
 
-def write_checkpoint(path, qwen_cfg=None, system1: str = "nextdit_async", seed: int = 0, shards: int = 2, s1_cfg=None):
+def write_checkpoint(path, qwen_cfg=None, system1: str = "nextdit_async", seed: int = 0, shards: int = 2, s1_cfg=None, generation_config=None):
     """A synthetic InternVLA-N1 checkpoint ON DISK in the layout of a real one (HF safetensors shards with the reference's parameter
     names + config.json in the Qwen2.5-VL / InternVLAN1ModelConfig layout): what `InternVLAN1ForCausalLM.from_pretrained` and the
-    agent's config-only construction are tested against (no real checkpoint is available offline). bf16 tensors, like the release."""
+    agent's config-only construction are tested against (no real checkpoint is available offline). bf16 tensors, like the release.
+    generation_config: a dict written as generation_config.json beside it (the default writes no such file)."""
     import json
     from pathlib import Path
 
@@ -671,4 +672,6 @@ def write_checkpoint(path, qwen_cfg=None, system1: str = "nextdit_async", seed: 
                             "out_hidden_size": cfg["v_out"], "fullatt_block_indexes": list(cfg["v_fullatt"]), "window_size": cfg["v_window"],
                             "patch_size": cfg["v_patch"], "spatial_merge_size": 2}}
     (p / "config.json").write_text(json.dumps(hf, indent=1))
+    if generation_config is not None:
+        (p / "generation_config.json").write_text(json.dumps(dict(generation_config), indent=1))
     return sd
