@@ -420,6 +420,25 @@ int ina_token_seen_set(uint32_t* seen, int32_t ld_words, const int32_t* ids, int
 int ina_argmax_penalty_rows(const float* X, int32_t ldx, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
                             int32_t* out, void* stream);
 
+/* ---- logprob_rows: log-softmax of a vocabulary row at ONE index, fused with the greedy selection - HF's generate(output_scores=True) +
+ *      compute_transition_scores(normalize_logits=True) without a [rows, vocab] tensor leaving the device; with `target`, the per-token
+ *      log-likelihood of caller-supplied tokens (teacher forcing).
+ *  y[r] is row r of X (f32 [rows, ldx], NOT modified): x itself with seen == NULL, else the repetition-penalised row of argmax_penalty_rows
+ *  (y = x < 0 ? x * penalty : x / penalty where the token's bit is set in seen[r], uint32 [rows, ld_words], ld_words * 32 >= n).
+ *  tok[r]:     target == NULL: the selection of argmax_rows / argmax_penalty_rows over y (first maximum, NaN never selected, a row without an
+ *              entry above -inf gives 0) - bit-equal to those kernels on the same input; mark != 0 (needs seen) then sets the chosen token's
+ *              bit in seen[r] in the same launch. target != NULL (int32 [rows]): tok[r] = target[r]; mark is refused. A target outside [0, n)
+ *              is an ignored label (HF's -100): logprob[r] = 0, margin[r] = 0, the row is not read.
+ *  logprob[r]: y[tok] - max(y) - log sum_j exp(y[j] - max(y)) in fp32 with expf / logf (= torch.log_softmax(y, -1)[tok]). A NaN anywhere in
+ *              the row gives NaN; -inf entries contribute 0; an all -inf row gives NaN.
+ *  margin[r]:  (may be NULL) y[tok] - the largest y at any OTHER index (NaN entries skipped; n == 1: +inf). >= 0 when tok was selected:
+ *              the top-2 margin of the decision.
+ *  One workgroup per row (any rows >= 0; rows == 0 launches nothing). Refusals (X / tok / logprob NULL, rows < 0, n < 1, ldx < n,
+ *  ld_words * 32 < n or a penalty that is not finite and > 0 when seen is set, mark without seen or with target) return non-zero before any
+ *  HIP call. Plain arguments: no struct, no ABI bump. */
+int ina_logprob_rows(const float* X, int32_t ldx, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
+                     const int32_t* target, int32_t* tok, float* logprob, float* margin, void* stream);
+
 /* ---- select_traj: per env, rank the S samples by critic value; neg = the k lowest (ascending), pos = the k highest
  *      (descending); trajectories are cumsum_t(sample * scale).  reference: navdp_policy.py:317-320. */
 typedef struct ina_select_args {

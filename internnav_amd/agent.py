@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from ._lib import EngineError
-from .policy import InternVLAN1ModelConfig, InternVLAN1Net, S1Output, S2Output
+from .policy import InternVLAN1ModelConfig, InternVLAN1Net, S1Output, S2Output, answer_confidences
 from .runtime import CapacityError
 
 _FATAL = (CapacityError, EngineError, MemoryError, KeyboardInterrupt)
@@ -87,7 +87,8 @@ class InternVLAN1Agent:
         checkpoint at model_settings['model_path'] on model_settings['device'] and the HF processor from the same path.
         model_settings read: model_path, device, policy_name, infer_mode ('sync' | 'partial_async'), sys2_max_forward_step, num_history,
         resize_w/h, width/height (camera), continuous_traj, env_num (engine capacity), repetition_penalty (optional: overrides the
-        checkpoint's generation_config.json), ignore_generation_config (optional), device_preprocess (optional), device_actions
+        checkpoint's generation_config.json), ignore_generation_config (optional), token_logprobs (optional, default False: every S2Output then
+        carries answer_logprob / answer_min_margin, the log-probability of the decoded answer and its smallest top-2 margin), device_preprocess (optional), device_actions
         (optional, default False: System-1's trajectories become the step's action table in one kernel launch instead of one numpy
         traj_to_actions per env; `last_action_table` then holds the int32 [n, 4] table of the last System-1 call on the device).
         Tests / bench may pass a built `model` + `processor`, or a `policy_factory() -> InternVLAN1Net`, instead."""
@@ -286,10 +287,14 @@ class InternVLAN1Agent:
                     pen = pens.pop()
                     if pen is not None:
                         gen_extra["repetition_penalty"] = float(pen)
+                    want_lp = bool(getattr(getattr(model, "qwen", None), "token_logprobs", False))     # model_settings['token_logprobs']
+                    if want_lp:
+                        gen_extra["output_logprobs"] = True
                     res = model.generate(input_ids=ids, pixel_values=pv, image_grid_thw=grid, max_new_tokens=128, do_sample=False, use_cache=True,
                                          past_key_values=pkv if any(c is not None for c in pkv) else None, return_dict_in_generate=True,
                                          **ragged, **gen_extra)
                     seqs = res.sequences
+                    conf = answer_confidences(res) if want_lp else None                    # one device-to-host copy for the chunk
                     if past:
                         self.kv_reuse_rows += model.last_kv_reuse["rows"]
                         self.kv_reuse_fallbacks += model.last_kv_reuse["fallbacks"]
@@ -323,7 +328,7 @@ class InternVLAN1Agent:
                 pending = []
                 for k, (e, o, inputs) in enumerate(items):
                     try:
-                        so = e.policy.finish_s2(inputs, seqs[k:k + 1], lambda: _PENDING)
+                        so = e.policy.finish_s2(inputs, seqs[k:k + 1], lambda: _PENDING, **({"confidence": conf[k]} if conf is not None else {}))
                     except _FATAL:
                         raise
                     except Exception as ex:  # noqa: BLE001 - e.g. IndexError on a one-number pixel goal (internvla_n1_policy.py:187)

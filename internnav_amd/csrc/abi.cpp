@@ -2,6 +2,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
+#include <cmath>
 
 #include "common.h"
 #include "kernels.h"
@@ -200,6 +201,19 @@ int ina_token_seen_set(uint32_t* seen, int32_t ld_words, const int32_t* ids, int
 int ina_argmax_penalty_rows(const float* X, int32_t ldx, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
                             int32_t* out, void* stream) {
     return ina_launch_argmax_penalty(X, ldx, rows, n, seen, ld_words, penalty, mark, out, reinterpret_cast<hipStream_t>(stream));
+}
+
+int ina_logprob_rows(const float* X, int32_t ldx, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
+                     const int32_t* target, int32_t* tok, float* logprob, float* margin, void* stream) {
+    INA_REQUIRE(X && tok && logprob, "logprob_rows: X, tok and logprob required");
+    INA_REQUIRE(rows >= 0 && n >= 1 && ldx >= n, "logprob_rows: bad arguments rows=%d n=%d ldx=%d (rows >= 0, n >= 1, ldx >= n)", rows, n, ldx);
+    if (seen) {
+        INA_REQUIRE((long)ld_words * 32 >= (long)n, "logprob_rows: ld_words=%d holds fewer than n=%d bits", ld_words, n);
+        INA_REQUIRE(std::isfinite(penalty) && penalty > 0.f, "logprob_rows: repetition penalty %g is not a strictly positive finite float", (double)penalty);
+    }
+    INA_REQUIRE(!mark || (seen && !target), "logprob_rows: mark needs a seen set and is refused with a target (teacher forcing selects nothing)");
+    if (rows == 0) return 0;
+    return ina_launch_logprob(X, ldx, rows, n, seen, ld_words, penalty, mark, target, tok, logprob, margin, reinterpret_cast<hipStream_t>(stream));
 }
 
 int ina_gemm_select(const ina_gemm_args* args, int* kernel) {

@@ -74,6 +74,8 @@ int ina_launch_token_seen_set(uint32_t* seen, int ld_words, const int32_t* ids, 
                               hipStream_t stream);                                                                           // decode_penalty.hip
 int ina_launch_argmax_penalty(const float* X, int ldx, int rows, int n, uint32_t* seen, int ld_words, float penalty, int mark, int32_t* out,
                               hipStream_t stream);                                                                           // decode_penalty.hip
+int ina_launch_logprob(const float* X, int ldx, int rows, int n, uint32_t* seen, int ld_words, float penalty, int mark, const int32_t* target,
+                       int32_t* tok, float* logprob, float* margin, hipStream_t stream);                                     // decode_logprob.hip
 int ina_launch_head3(const Head3Args& p, hipStream_t stream);
 int ina_launch_seqpool(const SeqpoolArgs& p, hipStream_t stream);
 int ina_launch_select(const SelectArgs& p, hipStream_t stream);

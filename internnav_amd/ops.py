@@ -640,6 +640,29 @@ def argmax_penalty_rows(x: torch.Tensor, seen: torch.Tensor, penalty: float, out
     return out
 
 
+def logprob_rows(x: torch.Tensor, tok: torch.Tensor, logprob: torch.Tensor, margin: Optional[torch.Tensor] = None, seen: Optional[torch.Tensor] = None,
+                 penalty: float = 1.0, mark: bool = False, target: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """logprob[r] = log_softmax(y[r])[tok[r]] of the f32 rows of x (not modified), y = x or, with `seen`, the repetition-penalised row of
+    argmax_penalty_rows. target None: tok[r] = the selection of argmax_rows / argmax_penalty_rows over y (bit-equal; mark sets the chosen bit in
+    seen[r]); target int32 [rows]: tok[r] = target[r] (teacher forcing; a target outside [0, n) is ignored: logprob 0, margin 0).
+    margin[r] (optional) = y[tok] - the largest y at any other index. tok int32 [rows], logprob / margin f32 [rows], contiguous."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    rows, n = x.shape
+    assert tok.dtype == torch.int32 and tok.numel() == rows and tok.is_contiguous()
+    for t in (logprob, margin):
+        assert t is None or (t.dtype == torch.float32 and t.numel() == rows and t.is_contiguous())
+    if seen is not None:
+        assert seen.dtype in (torch.uint32, torch.int32) and seen.dim() == 2 and seen.stride(1) == 1 and seen.shape[0] >= rows and seen.shape[1] * 32 >= n
+    if target is not None:
+        assert target.dtype == torch.int32 and target.numel() == rows and target.is_contiguous()
+    rc = _lib.lib().ina_logprob_rows(x.data_ptr(), x.stride(0), rows, n, seen.data_ptr() if seen is not None else None,
+                                     seen.stride(0) if seen is not None else 0, float(penalty), int(bool(mark)),
+                                     target.data_ptr() if target is not None else None, tok.data_ptr(), logprob.data_ptr(),
+                                     margin.data_ptr() if margin is not None else None, _stream())
+    _lib.check(rc, "logprob_rows")
+    return logprob
+
+
 def dit_v2t(kv2: torch.Tensor, heads: int, v2t: torch.Tensor) -> torch.Tensor:
     """condition V of a NextDiT block -> the transposed key-permuted image dit_attention consumes.
     kv2 bf16 [envs, Lz, 2, heads, 64] (K | V as produced by the fused kv projection); v2t bf16 [envs, heads, 64, 64]."""

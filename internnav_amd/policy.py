@@ -28,7 +28,7 @@ from typing import Any, Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import synthetic
+from . import ops, synthetic
 from .navdp import NavDPPolicyDAT
 from .nextdit import NextDiTSystem1
 from .qwen_vl import ATTN_WIDE_MIN_ROWS, SKINNY_GEMM_MAX_ROWS, EngineKVCache, QwenVLEngine, eos_ids, kv_reuse_fit, kv_reuse_lengths
@@ -122,6 +122,10 @@ class S2Output:
     output_latent: Optional[torch.Tensor] = None
     rgb_memory: Optional[np.ndarray] = None
     depth_memory: Optional[np.ndarray] = None
+    # model_settings['token_logprobs'] only (else None): log-probability of the decoded answer (sum over its tokens, EOS included) and the
+    # smallest top-2 margin among them (how close the answer came to being another one). Fields only: no policy decision reads them.
+    answer_logprob: Optional[float] = None
+    answer_min_margin: Optional[float] = None
 
     def validate(self) -> bool:
         return sum(x is not None for x in (self.output_action, self.output_pixel, self.output_latent)) > 0 and self.idx >= 0
@@ -212,6 +216,44 @@ def generation_config_from_hf(raw: Optional[dict], default_eos, ignore: bool = F
     return SimpleNamespace(repetition_penalty=pen, eos_token_id=eos_ids(default_eos if eos is None else eos), raw=raw)
 
 
+SCORE_SLAB_ROWS = 256      # rows of the fp32 [rows, vocab] logit buffer of score_answers (156 MB at 152064 tokens), allocated on first use
+
+
+def answer_logprob_summary(token_logprobs: torch.Tensor, token_margins: torch.Tensor, lengths) -> SimpleNamespace:
+    """the log-probability outputs of generate(): per-token values [B, n] of the emitted tokens and lengths [B] (tokens of each row up to and
+    including its first EOS) -> token_logprobs / token_margins with 0.0 at the positions behind it (a NaN there is dropped, one inside the
+    answer is kept), sequences_logprob [B] = the sum over the answer, answer_lengths int64 [B] = the lengths, on the device."""
+    lens = torch.as_tensor(np.asarray(lengths, dtype=np.int64), device=token_logprobs.device)
+    keep = torch.arange(token_logprobs.shape[1], device=token_logprobs.device)[None, :] < lens[:, None]
+    lp = torch.where(keep, token_logprobs.float(), torch.zeros((), device=token_logprobs.device))
+    mg = torch.where(keep, token_margins.float(), torch.zeros((), device=token_logprobs.device))
+    return SimpleNamespace(token_logprobs=lp, token_margins=mg, sequences_logprob=lp.sum(dim=1), answer_lengths=lens)
+
+
+def answer_confidences(res) -> List[Tuple[float, float]]:
+    """(answer_logprob, answer_min_margin) of every row of a generate(output_logprobs=True) result as Python floats: the sum of the answer's
+    token log-probabilities and the smallest top-2 margin among its tokens. ONE device-to-host copy for the whole batch."""
+    mg = res.token_margins
+    keep = torch.arange(mg.shape[1], device=mg.device)[None, :] < res.answer_lengths[:, None]
+    low = torch.where(keep, mg, torch.full((), float("inf"), device=mg.device)).min(dim=1).values if mg.shape[1] else torch.full_like(res.sequences_logprob, float("inf"))
+    both = torch.stack([res.sequences_logprob, low]).cpu().tolist()
+    return list(zip(both[0], both[1]))
+
+
+def score_row_plan(prompt_lens, answer_lens, slab_rows: int = SCORE_SLAB_ROWS):
+    """host plan of score_answers: sequence q = prompt_lens[q] prompt tokens followed by answer_lens[q] answer tokens, right-padded to the
+    longest. Answer token i of sequence q is predicted by the hidden row at position prompt_lens[q] - 1 + i of that sequence.
+    -> (S, rows int32 [R] = absolute rows q * S + position in sequence-major order, offsets int64 [Q + 1] of each sequence's rows in that order,
+    slabs = [(r0, r1), ...] consecutive row ranges of at most slab_rows rows)."""
+    pl, al = np.asarray(prompt_lens, dtype=np.int64).reshape(-1), np.asarray(answer_lens, dtype=np.int64).reshape(-1)
+    assert pl.shape == al.shape and pl.size > 0 and int(pl.min()) >= 1 and int(al.min()) >= 0 and slab_rows >= 1
+    S = int((pl + al).max())
+    off = np.concatenate([[0], np.cumsum(al)])
+    rows = np.concatenate([q * S + pl[q] - 1 + np.arange(al[q]) for q in range(pl.size)] + [np.zeros(0, dtype=np.int64)]).astype(np.int32)
+    R = int(off[-1])
+    return S, rows, off, [(r0, min(r0 + slab_rows, R)) for r0 in range(0, R, slab_rows)]
+
+
 class InternVLAN1ForCausalLM:
     """HF-style model object backed by the HIP engines (no nn.Module, no CPU fallback)."""
 
@@ -219,9 +261,12 @@ class InternVLAN1ForCausalLM:
                  device="cuda:0", max_envs: int = 16, max_seq_len: Optional[int] = None, max_patches: Optional[int] = None,
                  max_s2_seqs: Optional[int] = None, num_history: int = 8, resize_w: int = 384, resize_h: int = 384,
                  cam_w: int = 640, cam_h: int = 480, w8_decode: bool = False, generation_config: Optional[dict] = None,
-                 ignore_generation_config: bool = False):
+                 ignore_generation_config: bool = False, token_logprobs: bool = False, max_decode: int = 128):
         """Engine capacity defaults to the longest prompt the reference's harness can build for (num_history, resize, camera size):
-        see `s2_capacity`; exceeding it raises `CapacityError` (never a silent STOP)."""
+        see `s2_capacity`; exceeding it raises `CapacityError` (never a silent STOP).
+        token_logprobs (opt-in): the System-2 engine keeps the log-probability and top-2 margin of every greedy token
+        (generate(output_logprobs=True)) for answers of up to max_decode tokens (generate() refuses a larger max_new_tokens on such a model);
+        off, the launch sequence is the plain one."""
         self.device = torch.device(device)
         # the checkpoint's generation_config.json (None: no such file): generate() starts from it, as HF's does
         self.generation_config = generation_config_from_hf(generation_config, qwen_cfg["eos_token_id"], ignore=ignore_generation_config)
@@ -233,7 +278,8 @@ class InternVLAN1ForCausalLM:
         n_s2 = max_s2_seqs or max_envs   # System-2 runs on micro-batches of the envs whose plan expired (agent / bench schedule)
         cap_seq, cap_patches = s2_capacity(num_history, resize_w, resize_h, cam_w, cam_h, n_query=qwen_cfg["n_query"])
         self.qwen = QwenVLEngine(weights, qwen_cfg, device, max_seqs=n_s2, max_seq_len=max_seq_len or cap_seq,
-                                 max_patches=max_patches or n_s2 * cap_patches, w8_decode=w8_decode)
+                                 max_patches=max_patches or n_s2 * cap_patches, w8_decode=w8_decode, token_logprobs=token_logprobs, max_decode=max_decode)
+        self._score_logits = None       # fp32 [<= SCORE_SLAB_ROWS, vocab] of score_answers, allocated on first use
         if "nextdit" in system1:
             # the DiT's geometry (width, depth, heads, FFN width) is not in config.json - NextDiTCrossAttnConfig is constructed in code
             # (internvla_n1_arch.py:127-131) and its FFN width depends on the diffusers release (synthetic.lumina_ffn_width): read it off
@@ -300,7 +346,7 @@ class InternVLAN1ForCausalLM:
     def generate(self, input_ids=None, pixel_values=None, image_grid_thw=None, attention_mask=None, max_new_tokens: int = 128,
                  do_sample: bool = False, use_cache: bool = True, past_key_values=None, return_dict_in_generate: bool = False,
                  decode_chunk: int = 8, eos_token_id=None, cached_image_embeds: Optional[list] = None, prefix_kv: Optional[list] = None,
-                 export_prefix: Optional[list] = None, repetition_penalty: Optional[float] = None, **_):
+                 export_prefix: Optional[list] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False, **_):
         """greedy decoding (do_sample=False is the only mode the reference uses, internvla_n1_policy.py:169-176). Decodes in chunks of
         `decode_chunk` device-side steps and stops once every sequence has emitted EOS. Sequences are right-filled with EOS.
         repetition_penalty / eos_token_id: None = the checkpoint's generation_config.json (`self.generation_config`; without that file 1.0
@@ -319,8 +365,19 @@ class InternVLAN1ForCausalLM:
         token ids (cut back to an image boundary and so that the suffix still runs the kernels of a full prefill: exact). The caller vouches
         that cached images are the same images (only token ids are compared). pixel_values may hold every image or only the others.
         With return_dict_in_generate and use_cache the result carries `.past_key_values`: an EngineKVCache of every sequence's PROMPT
-        rows (not the answer: see EngineKVCache)."""
+        rows (not the answer: see EngineKVCache).
+        output_logprobs (with return_dict_in_generate; needs a model built with token_logprobs=True): the result also carries
+        `.token_logprobs` f32 [B, n] - per answer token the log-softmax of the PROCESSED scores (after the repetition penalty) at that token,
+        what HF's compute_transition_scores(sequences, scores, normalize_logits=True) returns -, `.token_margins` [B, n] (distance of the
+        chosen logit to the runner-up), `.sequences_logprob` [B] (the sum up to and including EOS) and `.answer_lengths` int64 [B] (tokens of
+        each answer up to and including its first EOS: the positions the sum runs over); positions behind a row's first EOS hold 0.0. output_scores / output_logits stay swallowed: no [B, vocab] tensor is returned."""
         assert not do_sample, "the reference only decodes greedily"
+        if output_logprobs and not self.qwen.token_logprobs:
+            raise ValueError("generate(output_logprobs=True) needs the engine setting token_logprobs: build the model with "
+                             "token_logprobs=True (from_pretrained(..., token_logprobs=True) / model_settings['token_logprobs'] = True)")
+        if self.qwen.token_logprobs and max_new_tokens > self.qwen.max_decode:
+            raise CapacityError(f"max_new_tokens={max_new_tokens} exceeds the max_decode={self.qwen.max_decode} log-probability columns of this "
+                                "token_logprobs model: build it with a larger max_decode (from_pretrained(..., max_decode=N))")
         eos_all = self.generation_config.eos_token_id if eos_token_id is None else eos_ids(eos_token_id)
         eos, eos_t = eos_all[0], torch.tensor(eos_all, dtype=torch.long)
         penalty = self.generation_config.repetition_penalty if repetition_penalty is None else float(repetition_penalty)
@@ -390,12 +447,95 @@ class InternVLAN1ForCausalLM:
         seqs = seqs.to(self.device)
         if not return_dict_in_generate:
             return seqs
+        lp_out = {}
+        if output_logprobs:
+            lp, mg = self.qwen.last_logprobs(state)            # one column per selection = per emitted token, chunked or not
+            assert lp.shape[1] == toks.shape[1], (lp.shape, toks.shape)
+            lp_out = vars(answer_logprob_summary(lp, mg, lens))
         # a prefill narrower than ATTN_WIDE_MIN_ROWS, or of SKINNY_GEMM_MAX_ROWS rows or fewer, ran other kernels than a full prefill of
         # a real prompt: only the rows it took from a cache are exact
         exact = int(state["S_run"]) >= ATTN_WIDE_MIN_ROWS and B * int(state["S_run"]) > SKINNY_GEMM_MAX_ROWS
         keep = plens if exact else np.broadcast_to(np.asarray(pl, dtype=np.int64), (B,))
         pkv = self.qwen.kv_handle([ids_cpu[b, : int(keep[b])] for b in range(B)]) if use_cache else None
-        return SimpleNamespace(sequences=seqs, past_key_values=pkv)
+        return SimpleNamespace(sequences=seqs, past_key_values=pkv, **lp_out)
+
+    def score_answers(self, input_ids, answers, pixel_values=None, image_grid_thw=None, attention_mask=None) -> SimpleNamespace:
+        """Teacher-forced scoring of caller-supplied answers: how likely is each candidate given its prompt?
+        input_ids int [B, S] (right-padded with attention_mask, as generate() takes them), answers: per prompt a list of candidate token-id
+        lists (append EOS to a candidate to have EOS scored). -> token_logprobs: per prompt, per candidate an f32 tensor [len] with
+        log P(token i | prompt, tokens < i); lengths (the same nesting, ints); sequences_logprob: per prompt an f32 tensor [candidates] of
+        the sums (device tensors).
+        The log-softmax runs over the RAW logits: NO repetition penalty is applied (under teacher forcing the seen set would differ at every
+        position; generate()'s token_logprobs are after the penalty - the two agree at penalty 1.0). Works without token_logprobs=True.
+        Every (prompt, candidate) pair is one right-padded sequence of a normal prefill (images are encoded per pair: a prompt with four
+        candidates runs the vision tower on its images four times), in groups of at most the engine's max_seqs pairs; the hidden rows that
+        predict answer tokens are gathered, normed and run through lm_head into an fp32 [<= 256, vocab] buffer, and ops.logprob_rows reads the
+        target tokens' log-probabilities off it."""
+        q = self.qwen
+        self._gen = None                                       # the cache slots are rewritten: generate_latents() must not continue an older generate()
+        ids_cpu = input_ids.cpu().long()
+        B, S0 = ids_cpu.shape
+        assert len(answers) == B, "answers: one list of candidates per prompt"
+        plens = np.full(B, S0, dtype=np.int64) if attention_mask is None else np.asarray(attention_mask.cpu().long().sum(1), dtype=np.int64)
+        grids = image_grid_thw.tolist() if image_grid_thw is not None else []
+        img_of = [[] for _ in range(B)]                        # images of each prompt (prompt order) and their patch rows in pixel_values
+        k = 0
+        for b in range(B):
+            left = int((ids_cpu[b, : plens[b]] == q.cfg["image_token_id"]).sum())
+            while left > 0:
+                t, h, w = (int(v) for v in grids[k])
+                img_of[b].append(k)
+                left -= t * h * w // 4
+                k += 1
+            assert left == 0, "image tokens and image_grid_thw disagree"
+        p_off = np.concatenate([[0], np.cumsum([int(t * h * w) for t, h, w in grids])]).astype(np.int64)
+        pv_all = pixel_values.to(self.device, torch.bfloat16) if pixel_values is not None and pixel_values.numel() else None
+        pairs = [(b, [int(t) for t in cand]) for b in range(B) for cand in answers[b]]
+        vocab = q.cfg["vocab"]
+        for b, cand in pairs:
+            assert all(0 <= t < vocab for t in cand), "answer token outside the vocabulary"
+        out_lp = {}
+        for g0 in range(0, len(pairs), q.B_max):
+            grp = pairs[g0:g0 + q.B_max]
+            pl, al = np.asarray([plens[b] for b, _ in grp]), np.asarray([len(c) for _, c in grp])
+            S, rows, off, slabs = score_row_plan(pl, al)
+            ids = torch.zeros(len(grp), S, dtype=torch.long)
+            for r, (b, cand) in enumerate(grp):
+                ids[r, : pl[r]] = ids_cpu[b, : pl[r]]
+                ids[r, pl[r]: pl[r] + al[r]] = torch.tensor(cand, dtype=torch.long)
+            imgs = [k for b, _ in grp for k in img_of[b]]
+            pv = torch.cat([pv_all[p_off[k]:p_off[k + 1]] for k in imgs], 0) if imgs else None
+            grid = image_grid_thw[imgs] if imgs else None
+            q.prefill(ids, pv, grid, seq_lens=pl + al)
+            R = int(off[-1])
+            if R == 0:
+                continue
+            rows_d = torch.from_numpy(rows).to(self.device)
+            tgt = torch.tensor([t for _, c in grp for t in c], dtype=torch.int32, device=self.device)
+            lp = torch.empty(R, dtype=torch.float32, device=self.device)
+            tok = torch.empty(R, dtype=torch.int32, device=self.device)
+            if self._score_logits is None:
+                self._score_logits = torch.empty(SCORE_SLAB_ROWS, vocab, dtype=torch.float32, device=self.device)
+                self._score_x = torch.empty(SCORE_SLAB_ROWS, q.H, dtype=torch.float32, device=self.device)
+                self._score_h = torch.empty(SCORE_SLAB_ROWS, q.H, dtype=torch.bfloat16, device=self.device)
+            for r0, r1 in slabs:
+                m = r1 - r0
+                x, h, logits = self._score_x[:m], self._score_h[:m], self._score_logits[:m]
+                ops.gather_rows(q.x[: len(grp) * S], x, src=rows_d[r0:r1])
+                ops.norm(x, q.norm_w, None, eps=1e-6, rms=True, out=h, rows=m)
+                ops.linear(h, q.lm_head, out=logits)
+                ops.logprob_rows(logits, tok[r0:r1], lp[r0:r1], target=tgt[r0:r1])
+            for r in range(len(grp)):
+                out_lp[g0 + r] = lp[off[r]:off[r + 1]]
+        res_lp, res_len, res_sum, i = [], [], [], 0
+        for b in range(B):
+            n = len(answers[b])
+            per = [out_lp.get(i + c, torch.empty(0, dtype=torch.float32, device=self.device)) for c in range(n)]
+            res_lp.append(per)
+            res_len.append([int(t.numel()) for t in per])
+            res_sum.append(torch.stack([t.sum() for t in per]) if per else torch.empty(0, dtype=torch.float32, device=self.device))
+            i += n
+        return SimpleNamespace(token_logprobs=res_lp, lengths=res_len, sequences_logprob=res_sum)
 
     def _import_past(self, input_ids, plens, pv, image_grid_thw, past, cached_image_embeds, tail):
         """generate(past_key_values=...): reused prompt lengths per sequence, the cached rows put into the batch's cache slots, and
@@ -616,7 +756,8 @@ class InternVLAN1Net:
     @classmethod
     def _load(cls, ms: dict):
         """model + processor for a model_settings dict, loaded once per (checkpoint, device) and shared afterwards."""
-        key = (str(ms["model_path"]), str(ms.get("device", "cuda:0")), bool(ms.get("w8_decode", False)), bool(ms.get("ignore_generation_config", False)))
+        key = (str(ms["model_path"]), str(ms.get("device", "cuda:0")), bool(ms.get("w8_decode", False)), bool(ms.get("ignore_generation_config", False)),
+               bool(ms.get("token_logprobs", False)))
         if key not in cls._shared:
             n_env = int(ms.get("env_num", 1) or 1)
             model = InternVLAN1ForCausalLM.from_pretrained(
@@ -624,7 +765,8 @@ class InternVLAN1Net:
                 max_envs=max(n_env, int(ms.get("max_envs", 1))), max_s2_seqs=ms.get("max_s2_seqs"), num_history=ms.get("num_history", 8),
                 resize_w=ms.get("resize_w", 384), resize_h=ms.get("resize_h", 384), cam_w=ms.get("width", 640), cam_h=ms.get("height", 480),
                 w8_decode=bool(ms.get("w8_decode", False)),      # System-2 single-token passes on FP8 weights (QwenVLEngine(w8_decode=True))
-                ignore_generation_config=bool(ms.get("ignore_generation_config", False)))
+                ignore_generation_config=bool(ms.get("ignore_generation_config", False)),
+                token_logprobs=bool(ms.get("token_logprobs", False)))   # per-token log-probabilities of System-2 answers (S2Output.answer_logprob)
             cls._shared[key] = (model.eval(), cls.load_processor(ms["model_path"]))
         return cls._shared[key]
 
@@ -804,10 +946,13 @@ class InternVLAN1Net:
                 new[key] = (e, grids[k])
         self._emb_cache = new
 
-    def finish_s2(self, inputs, output_ids, latents_fn) -> S2Output:
-        """steps 3-4 of s2_step (internvla_n1_policy.py:177-197): decode text, pixel goal -> latents, else discrete actions."""
+    def finish_s2(self, inputs, output_ids, latents_fn, confidence=None) -> S2Output:
+        """steps 3-4 of s2_step (internvla_n1_policy.py:177-197): decode text, pixel goal -> latents, else discrete actions.
+        confidence: (answer_logprob, answer_min_margin) of this row when the model keeps token log-probabilities, else None."""
         self.llm_output = self.processor.tokenizer.decode(output_ids[0][inputs["input_ids"].shape[1]:], skip_special_tokens=True)
         out = S2Output()
+        if confidence is not None:
+            out.answer_logprob, out.answer_min_margin = confidence
         if re.search(r"\d", self.llm_output):
             coord = [int(c) for c in re.findall(r"\d+", self.llm_output)]
             out.output_pixel = np.array([int(coord[1]), int(coord[0])])   # a one-number answer raises IndexError like the reference (:187) -> the agent's retry path
@@ -832,9 +977,13 @@ class InternVLAN1Net:
             past = [past] if past is not None else None
         if self.repetition_penalty is not None:
             extra["repetition_penalty"] = float(self.repetition_penalty)
+        want_lp = bool(getattr(getattr(self.model, "qwen", None), "token_logprobs", False))
+        if want_lp:
+            extra["output_logprobs"] = True
         res = self.model.generate(input_ids=inputs["input_ids"], pixel_values=inputs["pixel_values"], image_grid_thw=inputs["image_grid_thw"],
                                   max_new_tokens=128, do_sample=False, use_cache=True, past_key_values=past, return_dict_in_generate=True, **extra)
         ids = res.sequences
+        conf = answer_confidences(res)[0] if want_lp else None
         if self.kv_reuse:
             self.store_kv(inputs, res.past_key_values)
         del res
@@ -844,7 +993,8 @@ class InternVLAN1Net:
             self.store_prefix(inputs, self.model.last_prefix_kv()[0])
         extra = {k: v for k, v in extra.items() if k == "cached_image_embeds"}
         try:
-            return self.finish_s2(inputs, ids, lambda: self.model.generate_latents(ids, inputs["pixel_values"], inputs["image_grid_thw"], **extra))
+            return self.finish_s2(inputs, ids, lambda: self.model.generate_latents(ids, inputs["pixel_values"], inputs["image_grid_thw"], **extra),
+                                  **({"confidence": conf} if want_lp else {}))
         except Exception:
             self._kv = None
             raise

@@ -269,7 +269,10 @@ class QwenVLEngine:
     """weights: mapping key -> tensor (a state dict, or a lazy provider that materialises tensors on the device)."""
 
     def __init__(self, weights, cfg: dict, device="cuda:0", max_seqs: int = 16, max_seq_len: int = 1024, max_patches: int = 16 * 3136,
-                 frag_weights: Optional[bool] = None, w8_decode: bool = False):
+                 frag_weights: Optional[bool] = None, w8_decode: bool = False, token_logprobs: bool = False, max_decode: int = 128):
+        """token_logprobs (opt-in, fixed for the engine's life: captured graphs and cached models are of one setting): every greedy selection
+        also writes the log-probability and the top-2 margin of the chosen token (ops.logprob_rows IN PLACE of the argmax launch: same launch
+        count, same tokens) into per-step device buffers for up to max_decode answer tokens; read them with `last_logprobs`."""
         dev = torch.device(device)
         bf, f32 = torch.bfloat16, torch.float32
         self.cfg, self.device = cfg, dev
@@ -374,6 +377,13 @@ class QwenVLEngine:
         # repetition penalty (generation_config.json, HF RepetitionPenaltyLogitsProcessor): per sequence the bitmap of the tokens seen so far
         # (token t = bit t & 31 of word t >> 5; rows of a multiple of 4 words). Only a call with a penalty != 1 ever touches it.
         self.seen = torch.zeros(max_seqs, ((cfg["vocab"] + 31) // 32 + 3) // 4 * 4, dtype=torch.uint32, device=dev)
+        # token_logprobs: log-probability / top-2 margin of answer token j of sequence b at [b, j]. Stored step-major, so the column a step's
+        # launch writes is one contiguous row at an address fixed per step (capturable); tok_logprob / tok_margin are the [B_max, max_decode] views
+        self.token_logprobs, self.max_decode = bool(token_logprobs), int(max_decode)
+        self._lp_steps = self._mg_steps = self.tok_logprob = self.tok_margin = None      # (no buffer at all without the setting)
+        if self.token_logprobs:
+            self._lp_steps, self._mg_steps = (torch.zeros(self.max_decode, max_seqs, dtype=f32, device=dev) for _ in range(2))
+            self.tok_logprob, self.tok_margin = self._lp_steps.t(), self._mg_steps.t()
         half = self.hd // 2
         self.inv_freq = (1.0 / (cfg["rope_theta"] ** (torch.arange(0, self.hd, 2, dtype=f32) / self.hd))).to(dev)
         axis = np.concatenate([np.full(16, 0), np.full(24, 1), np.full(24, 2)]).astype(np.int32)  # mrope_section [16, 24, 24]
@@ -398,6 +408,9 @@ class QwenVLEngine:
         t = copy.copy(self)
         for n in self._BUFFERS:
             setattr(t, n, torch.empty_like(getattr(self, n)))
+        if self.token_logprobs:
+            t._lp_steps, t._mg_steps = torch.zeros_like(self._lp_steps), torch.zeros_like(self._mg_steps)
+            t.tok_logprob, t.tok_margin = t._lp_steps.t(), t._mg_steps.t()
         t.layers = [dict(L, kv=torch.empty_like(L["kv"])) for L in self.layers]
         t._side = None
         t._kv_reset_tracking()
@@ -568,10 +581,11 @@ class QwenVLEngine:
             if self.tap is not None:
                 self.tap("llm", li, x)
 
-    def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None, penalty: Optional[float] = None):
+    def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None, penalty: Optional[float] = None, col: int = 0):
         """final RMSNorm + lm_head on ONE row per sequence, greedy argmax on the device. row_in_seq: the same row for every sequence,
         or (ragged batches) rows_idx int32 [B] = absolute row of each sequence's last real token. penalty: the selection runs over the
-        repetition-penalised logits of the tokens in `seen` and marks the chosen one (`logits` keeps the raw values)."""
+        repetition-penalised logits of the tokens in `seen` and marks the chosen one (`logits` keeps the raw values).
+        col (token_logprobs engines): the answer position this selection produces = the column of tok_logprob / tok_margin it fills."""
         if rows_idx is not None:
             ops.gather_rows(self.x[: B * S], self.xl[:B], src=rows_idx)
             ops.norm(self.xl[:B], self.norm_w, None, eps=1e-6, rms=True, out=self.hl[:B], rows=B)
@@ -581,10 +595,26 @@ class QwenVLEngine:
             ops.linear_w8(self.hl[:B], *self.lm_head8, out=self.logits[:B])
         else:
             ops.linear(self.hl[:B], self.lm_head, out=self.logits[:B])     # (152064 columns: one wave per 16-column tile owns all of K)
-        if penalty is None:
+        if self.token_logprobs:
+            # the same selection (bit-equal ids) + log-softmax at the chosen index and the top-2 margin, in the launch that replaces the argmax
+            assert col < self.max_decode, (col, self.max_decode)     # (plan() / decode() refuse longer answers before anything is launched)
+            ops.logprob_rows(self.logits[:B], self.next_tok[:B], self._lp_steps[col, :B], self._mg_steps[col, :B],
+                             seen=None if penalty is None else self.seen, penalty=1.0 if penalty is None else penalty, mark=penalty is not None)
+        elif penalty is None:
             ops.argmax_rows(self.logits[:B], self.next_tok[:B])
         else:
             ops.argmax_penalty_rows(self.logits[:B], self.seen, penalty, self.next_tok[:B], mark=True)
+
+    def last_logprobs(self, state: dict):
+        """(logprob, margin) f32 [B, n] device views: one value per answer token selected so far from `state` (what `prefill` returned and
+        `decode` advanced, or a plan after `run_decode`: all n_decode positions). logprob = log_softmax of the repetition-penalised logits at
+        the chosen token (HF compute_transition_scores(normalize_logits=True) on processed scores), margin = its distance to the runner-up.
+        Views of the engine's buffers: the next call overwrites them."""
+        if not self.token_logprobs:
+            raise RuntimeError("this engine was built without token_logprobs=True (QwenVLEngine(..., token_logprobs=True) / "
+                               "model_settings['token_logprobs'] / from_pretrained(token_logprobs=True))")
+        n = int(state["n_sel"]) if "n_sel" in state else int(state.get("n_decode", 0))
+        return self.tok_logprob[: state["B"], :n], self.tok_margin[: state["B"], :n]
 
     def _seen_init(self, P: dict):
         """launch in front of a decode's first selection: every sequence's seen set = its whole prompt (cached prefix included)"""
@@ -617,6 +647,8 @@ class QwenVLEngine:
         B, S = ids.shape
         if B > self.B_max or S > self.S_max:
             raise CapacityError(f"System-2 batch of {B} x {S} tokens exceeds the engine's max_seqs={self.B_max} / max_seq_len={self.S_max}")
+        if self.token_logprobs and n_decode > self.max_decode:      # here, not inside run_decode: that may run under a graph capture
+            raise CapacityError(f"n_decode={n_decode} answer tokens exceed the engine's max_decode={self.max_decode} log-probability columns")
         pl = np.broadcast_to(np.asarray(prefix_len, dtype=np.int64).reshape(-1), (B,)).copy()
         assert int(pl.min()) >= 0 and int(pl.max()) < S, f"prefix_len={pl.tolist()} must leave at least one token of the {S}-token prompts to run"
         # the planned decode / latent passes read every sequence's first token at row S_run - 1 of its rectangle: only uniform prefixes put
@@ -785,14 +817,14 @@ class QwenVLEngine:
         if j0 == 0:
             if pen is not None:
                 self._seen_init(P)                                # part of the launch sequence: a captured decode re-initialises the set on replay
-            self._last_logits(B, S, S - 1, penalty=pen)
+            self._last_logits(B, S, S - 1, penalty=pen, col=0)
         for j in range(j0, j1):
             tokens_out[:, j].copy_(self.next_tok[:B])
             if j == n - 1:
                 break
             ops.gather_rows(self.embed, self.x_in, src=self.next_tok[:B], rows=B)
             self._layers(P["decode"][j])
-            self._last_logits(B, 1, 0, penalty=pen)
+            self._last_logits(B, 1, 0, penalty=pen, col=j + 1)
 
     def run_latents(self, P: dict, out: torch.Tensor):
         """N_QUERY latent queries (behind the last sampled token) against the KV cache -> out bf16 [B, N_QUERY, H]."""
@@ -967,20 +999,24 @@ class QwenVLEngine:
         out = torch.empty(B, n_steps, dtype=torch.int32, device=self.device)
         lens = state.get("lens")
         pen = state["plan"].get("rep_penalty")
+        if self.token_logprobs and state.get("n_sel", 1) + n_steps - 1 > self.max_decode:      # before anything is launched
+            raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} exceeds the engine's max_decode={self.max_decode} "
+                                "log-probability columns")
         if "cur" not in state:
             if pen is not None:
                 self._seen_init(state["plan"])
             if lens is None and bool((state["plan"]["prefix_len"] == state["plan"]["prefix_len"][0]).all()):
-                self._last_logits(B, Sr, Sr - 1, penalty=pen)
+                self._last_logits(B, Sr, Sr - 1, penalty=pen, col=0)
                 state["cur"] = S
             elif lens is None:       # equal-length prompts behind prefixes of different lengths: each sequence's last real row
                 rows = torch.from_numpy((np.arange(B) * Sr + S - state["plan"]["prefix_len"] - 1).astype(np.int32)).to(self.device)
-                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen)
+                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen, col=0)
                 state["cur"] = S
             else:
                 rows = torch.from_numpy((np.arange(B) * Sr + lens - state["plan"]["prefix_len"] - 1).astype(np.int32)).to(self.device)
-                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen)
+                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen, col=0)
                 state["cur"] = lens.copy()
+            state["n_sel"] = 1                                    # selections made so far = answer tokens with a log-probability column
         for j in range(n_steps):
             out[:, j].copy_(self.next_tok[:B])
             if j == n_steps - 1:
@@ -991,7 +1027,8 @@ class QwenVLEngine:
                 self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur))
             else:
                 self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur, k_len=cur + 1))
-            self._last_logits(B, 1, 0, penalty=pen)
+            self._last_logits(B, 1, 0, penalty=pen, col=state["n_sel"])
+            state["n_sel"] += 1
             state["cur"] = cur + 1
             state["next_pos"] = state["next_pos"] + 1
         return out
