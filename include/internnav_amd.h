@@ -268,6 +268,28 @@ int ina_goal_slots(void* Y, int32_t ldy, int32_t y_dtype, int32_t L, int32_t slo
 int ina_kv_copy(int32_t to_engine, const int64_t* layer_base, int32_t n_layers, const int64_t* seq, int32_t n_seq, int64_t engine_rows,
                 int64_t row_bytes, int64_t max_rows, void* stream);
 
+/* ---- attention_prefix: causal self-attention of P short suffixes that also see a prefix kept ONCE in the System-2 KV cache, one launch
+ *      (teacher-forced scoring of several candidate answers behind one prefilled prompt: score_answers(share_prefix=True)).
+ *  bf16 in / out, fp32 softmax and accumulation, strides in elements, D = 128.
+ *  Q, O       P pairs x m rows x H heads x D: element (p, i, h, d) at p * ?_ps + i * ?_rs + h * ?_hs + d;
+ *  k_cache, v_cache   the engine's cache layout: key / value row r of slot s, KV head kh at s * c_ss + r * c_rs + kh * c_hs (one set of
+ *             strides for both pointers), n_slots slots, at least max_pfx rows in each;
+ *  k_suf, v_suf       the pairs' own keys / values (the k and v columns of the q|k|v projection after the in-place rotary embedding):
+ *             row j of pair p, KV head kh at p * s_ps + j * s_rs + kh * s_hs (one set of strides for both pointers);
+ *  slot, pfx_len, suf_len   device int32 [P].
+ *  Query row i of pair p, i < suf_len[p], sees keys 0 .. min(pfx_len[p], max_pfx) - 1 of cache slot slot[p] and suffix keys j <= i of
+ *  pair p: nothing of another pair, no cache row at or behind pfx_len[p]. pfx_len 0 = plain causal self-attention over the suffix.
+ *  Output rows i >= suf_len[p] are written as zeros. A slot[p] outside [0, n_slots) yields NaN in the rows i < suf_len[p] of that pair
+ *  and never an out-of-bounds access. Nothing is written to the cache. No atomics, no workspace: two launches give the same bits;
+ *  device tables only: graph capturable.
+ *  Contract: D = 128, H % Hkv = 0, 1 <= m <= 64 (the suffix is one 64-key chunk), suf_len <= m (clipped), max_pfx >= 0, n_slots >= 1,
+ *  16-byte aligned Q / K / V rows (strides multiples of 8, pointers of 16 bytes), 8-byte aligned O rows; anything else is refused before
+ *  any HIP call. P = 0 returns 0 and launches nothing. Plain arguments: no struct, no ABI bump. */
+int ina_attention_prefix(const void* Q, int64_t q_ps, int64_t q_rs, int64_t q_hs, void* O, int64_t o_ps, int64_t o_rs, int64_t o_hs,
+                         const void* k_cache, const void* v_cache, int64_t c_ss, int64_t c_rs, int64_t c_hs, int32_t n_slots, const void* k_suf,
+                         const void* v_suf, int64_t s_ps, int64_t s_rs, int64_t s_hs, const int32_t* slot, const int32_t* pfx_len,
+                         const int32_t* suf_len, int32_t P, int32_t m, int32_t H, int32_t Hkv, int32_t D, int32_t max_pfx, float scale, void* stream);
+
 /* ---- memory_gather: the visual-memory rows of the NavDPNet former's token buffer for n stepped envs of a rollout, from a per-env ring of
  *      cached frame tokens, in ONE launch (graph capturable; reference memory semantics: navdp_lerobot_dataset.py:215-222).
  *  ring  f32 [max_envs, depth, ntok, C]: final-LayerNorm tokens of each env's last depth = (M - 1) * stride + 1 frames, without positions;

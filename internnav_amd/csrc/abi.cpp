@@ -182,6 +182,15 @@ int ina_kv_copy(int32_t to_engine, const int64_t* layer_base, int32_t n_layers, 
                               reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_attention_prefix(const void* Q, int64_t q_ps, int64_t q_rs, int64_t q_hs, void* O, int64_t o_ps, int64_t o_rs, int64_t o_hs,
+                         const void* k_cache, const void* v_cache, int64_t c_ss, int64_t c_rs, int64_t c_hs, int32_t n_slots, const void* k_suf,
+                         const void* v_suf, int64_t s_ps, int64_t s_rs, int64_t s_hs, const int32_t* slot, const int32_t* pfx_len,
+                         const int32_t* suf_len, int32_t P, int32_t m, int32_t H, int32_t Hkv, int32_t D, int32_t max_pfx, float scale, void* stream) {
+    return ina_launch_attention_prefix(Q, (long)q_ps, (long)q_rs, (long)q_hs, O, (long)o_ps, (long)o_rs, (long)o_hs, k_cache, v_cache, (long)c_ss,
+                                       (long)c_rs, (long)c_hs, n_slots, k_suf, v_suf, (long)s_ps, (long)s_rs, (long)s_hs, slot, pfx_len, suf_len, P, m,
+                                       H, Hkv, D, max_pfx, scale, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_memory_gather(void* out, int64_t out_env_stride, float* ring, const float* fresh, const float* blank, const float* pe, const int32_t* env,
                       const int32_t* head, const int32_t* count, int32_t n, int32_t max_envs, int32_t M, int32_t ntok, int32_t C, int32_t depth,
                       int32_t stride, void* stream) {

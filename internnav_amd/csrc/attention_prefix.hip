@@ -1,0 +1,279 @@
+// Shared-prefix attention for gfx950 (bf16 in/out, fp32 softmax + accumulation, d = 128): P (prompt, candidate) pairs, each a short causal
+// SUFFIX of m rows that also sees a PREFIX kept once per prompt in the System-2 KV cache (score_answers(share_prefix=True): the prompt is
+// prefilled once into its cache slot, only the candidates' own tokens run through the stack).
+//
+//   query row i of pair p (i < suf_len[p]) sees  keys 0 .. pfx_len[p] - 1 of cache slot slot[p]   (the prefix, read in place)
+//                                          and   suffix keys j <= i of pair p                     (read from the q|k|v projection buffer)
+//
+// nothing of another pair, no cache row at or behind pfx_len[p]. Nothing is written to the cache.
+//
+// Structure: the one-launch decode kernels of attention.hip. The G = H / Hkv query heads of a KV head and their m positions are the ROWS of
+// 16-row MFMA tiles (row R -> head kh * G + R / m, position R % m); one four-wave workgroup per (pair, KV head, row tile). The key axis is cut in
+// 64-key chunks: chunks 0 .. nc - 1 are the prefix, chunk nc is the (single, causal) suffix chunk; wave w walks chunks w, w + 4, ... with a running
+// (max, sum, O) in registers. K fragments come straight from global memory in MFMA operand layout, V goes through a wave-private transposed LDS
+// image (vt_pos of attention.hip), the next chunk is requested before the current one is multiplied. The four partials meet in LDS in wave
+// order and the workgroup writes the normalised rows itself: no atomics, no workspace, the same bits on every launch.
+// Workgroups of the pairs that share a slot are neighbours in the grid (pair index runs faster than the KV head), so that the first of them brings
+// the prompt's K/V of that head in from HBM and the others can find it in L2 / Infinity Cache (an expectation: no counter was read).
+// Resources: 256 VGPRs + 129 AGPRs (two chunks' K fragments and V pieces live across the prefetch), no scratch -> one workgroup per CU.
+#include <cmath>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+
+constexpr int PFX_WAVES = 4, PFX_CHUNK = 64, PFX_D = 128;
+
+// key permutation of the V^T image (attention.hip, vt_pos): MFMA k index g*8 + j <-> key (j < 4 ? g*4 + j : 16 + g*4 + (j - 4)) per 32-key sub-block
+__device__ __forceinline__ int pfx_vt_pos(int kv_local) {
+    int sub = kv_local >> 5, w = kv_local & 31;
+    int t = w >> 4, x = w & 15;
+    return (sub << 5) + ((x >> 2) << 3) + (x & 3) + (t << 2);
+}
+
+struct PrefixArgs {
+    const bf16* Q; bf16* O;
+    const bf16 *Kc, *Vc, *Ks, *Vs;
+    const int32_t *slot, *pfx_len, *suf_len;
+    long q_ps, q_rs, q_hs, o_ps, o_rs, o_hs, c_ss, c_rs, c_hs, s_ps, s_rs, s_hs;
+    int P, m, H, Hkv, n_slots, max_pfx, rtiles;
+    float scale;
+};
+
+__global__ __launch_bounds__(PFX_WAVES * 64) void attn_prefix_kernel(PrefixArgs a) {
+    constexpr int D = PFX_D, KVB = PFX_CHUNK, VT_LD = KVB + 8, VCPR = D / 8, NKK = D / 32, NST = KVB / 16, NSB = KVB / 32, NDT = D / 16;
+    constexpr int PER_WAVE = D * VT_LD;                       // bf16 elements of one wave's V^T image
+    constexpr int PLD = D + 4;                                // partial row: D x O, m, l (f32), padded to a 16-byte pitch (f32x4 stores)
+    constexpr int CPT = D / 16;                               // output columns per thread in the combine
+    static_assert(16 * PLD * 4 <= PER_WAVE * 2, "the partial of a wave fits its V^T image");
+    extern __shared__ __attribute__((aligned(16))) char pfx_smem[];
+    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, lq = lane & 15;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    bf16* Vt = reinterpret_cast<bf16*>(pfx_smem) + wave * PER_WAVE;
+    const int rt = blockIdx.x % a.rtiles, p = blockIdx.x / a.rtiles, kh = blockIdx.y;
+    const int G = a.H / a.Hkv;
+    const int sl = a.slot[p];
+    const int pfx = min(max(a.pfx_len[p], 0), a.max_pfx);
+    const int suf = min(max(a.suf_len[p], 0), a.m);
+    const bool bad_slot = sl < 0 || sl >= a.n_slots;
+    bf16* __restrict__ O = a.O + (size_t)p * a.o_ps;
+
+    if (bad_slot || suf == 0) {
+        // nothing to attend (zeros), or a slot outside the cache: NaN in the pair's live rows (the library's convention), never an access
+        const int row = tid >> 4, c0 = (tid & 15) * CPT;
+        const int Rr = rt * 16 + row;
+        if (Rr < G * a.m) {
+            const int hd = kh * G + Rr / a.m, qp = Rr % a.m;
+            const bf16 fill = (bf16)((bad_slot && qp < suf) ? NAN : 0.f);
+            const bf16x4 f4 = {fill, fill, fill, fill};
+            bf16* op = O + (size_t)qp * a.o_rs + (size_t)hd * a.o_hs + c0;
+            *reinterpret_cast<bf16x4*>(op) = f4;
+            *reinterpret_cast<bf16x4*>(op + 4) = f4;
+        }
+        return;
+    }
+
+    const int R = rt * 16 + lq;                                // packed row of this lane
+    const bool live = R < G * a.m;
+    const int head = kh * G + (live ? R / a.m : 0), qpos = live ? R % a.m : 0;
+    const bool active = live && qpos < suf;                    // rows at or behind suf_len attend nothing: zeros
+    const bf16* __restrict__ Q = a.Q + (size_t)p * a.q_ps + (size_t)qpos * a.q_rs + (size_t)head * a.q_hs;
+    const bf16* __restrict__ Kc = a.Kc + (size_t)sl * a.c_ss + (size_t)kh * a.c_hs;
+    const bf16* __restrict__ Vc = a.Vc + (size_t)sl * a.c_ss + (size_t)kh * a.c_hs;
+    const bf16* __restrict__ Ks = a.Ks + (size_t)p * a.s_ps + (size_t)kh * a.s_hs;
+    const bf16* __restrict__ Vs = a.Vs + (size_t)p * a.s_ps + (size_t)kh * a.s_hs;
+    const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+
+    float m_run = -INFINITY, l_run = 0.f;
+    f32x4 acc_o[NDT];
+#pragma unroll
+    for (int i = 0; i < NDT; ++i) acc_o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    bf16x8 qf[NKK];
+#pragma unroll
+    for (int kk = 0; kk < NKK; ++kk) qf[kk] = active ? *reinterpret_cast<const bf16x8*>(Q + kk * 32 + g * 8) : zero8;
+
+    const int nc = (pfx + KVB - 1) / KVB;                      // prefix chunks; chunk nc is the suffix
+    constexpr int NVI = KVB * VCPR / 64;
+    static_assert((KVB * VCPR) % 64 == 0, "chunk pieces must divide evenly over the wave");
+    bf16x8 kf[NST][NKK], vreg[NVI];
+    // chunk c of this pair: (K base, V base, row stride, first key, keys of the source) - wave uniform
+    auto fetch = [&](int c) {
+        const bool sfx = c == nc;
+        const bf16* Kb = sfx ? Ks : Kc;
+        const bf16* Vb = sfx ? Vs : Vc;
+        const long rs = sfx ? a.s_rs : a.c_rs;
+        const int kv0 = sfx ? 0 : c * KVB, len = sfx ? suf : pfx;
+#pragma unroll
+        for (int t = 0; t < NST; ++t) {
+            const int kv = kv0 + t * 16 + lq;
+            const bf16* kr = Kb + (size_t)(kv < len ? kv : len - 1) * rs + g * 8;      // (keys beyond len: a valid row, their scores are masked)
+#pragma unroll
+            for (int kk = 0; kk < NKK; ++kk) kf[t][kk] = *reinterpret_cast<const bf16x8*>(kr + kk * 32);
+        }
+#pragma unroll
+        for (int u = 0; u < NVI; ++u) {
+            const int q = lane + u * 64, row = q / VCPR, cc = q % VCPR, kv = kv0 + row;
+            vreg[u] = (kv < len) ? *reinterpret_cast<const bf16x8*>(Vb + (size_t)kv * rs + cc * 8) : zero8;
+        }
+    };
+    const float sc = a.scale * 1.4426950408889634f;            // exp2 domain
+    int c = wave;
+    if (c <= nc) fetch(c);
+    for (; c <= nc; c += PFX_WAVES) {
+        const bool sfx = c == nc;
+        const int kv0 = sfx ? 0 : c * KVB, len = sfx ? suf : pfx;
+        // ---- S^T = K Q^T from the register fragments
+        f32x4 s[NST];
+#pragma unroll
+        for (int t = 0; t < NST; ++t) {
+            s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kk = 0; kk < NKK; ++kk) s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t][kk], qf[kk], s[t], 0, 0, 0);
+        }
+        // ---- V registers -> this wave's transposed image (the reads of the previous chunk were consumed by its MFMAs: the LDS queue of a wave is in order)
+#pragma unroll
+        for (int u = 0; u < NVI; ++u) {
+            const int q = lane + u * 64, row = q / VCPR, cc = q % VCPR;
+            const int pos = pfx_vt_pos(row);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) Vt[(cc * 8 + i) * VT_LD + ((pos + 8 * cc) & (KVB - 1))] = vreg[u][i];   // rotated rows: see vt_pos
+        }
+        if (c + PFX_WAVES <= nc) fetch(c + PFX_WAVES);          // next chunk in flight under this one's math
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        // ---- mask + online softmax (lane owns packed row R, keys kv0 + t*16 + g*4 + r)
+        float mx = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < NST; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int kv = kv0 + t * 16 + g * 4 + r;
+                const bool ok = active && kv < len && (!sfx || kv <= qpos);
+                const float v = ok ? s[t][r] * sc : -INFINITY;
+                s[t][r] = v;
+                mx = fmaxf(mx, v);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float m_new = fmaxf(m_run, mx);
+        const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
+        const float alpha = (m_run == -INFINITY) ? 0.f : exp2f(m_run - m_use);
+        float rs = 0.f;
+#pragma unroll
+        for (int t = 0; t < NST; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float e = exp2f(s[t][r] - m_use);
+                s[t][r] = e;
+                rs += e;
+            }
+        rs += __shfl_xor(rs, 16);
+        rs += __shfl_xor(rs, 32);
+        l_run = l_run * alpha + rs;
+        m_run = m_new;
+#pragma unroll
+        for (int nt = 0; nt < NDT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc_o[nt][r] *= alpha;
+        // ---- O^T += V^T P^T
+#pragma unroll
+        for (int sb = 0; sb < NSB; ++sb) {
+            bf16x8 pf;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                pf[r] = (bf16)s[2 * sb][r];
+                pf[4 + r] = (bf16)s[2 * sb + 1][r];
+            }
+#pragma unroll
+            for (int nt = 0; nt < NDT; ++nt) {
+                const bf16x8 vf = *reinterpret_cast<const bf16x8*>(&Vt[(nt * 16 + lq) * VT_LD + ((sb * 32 + g * 8 + 8 * ((nt * 16 + lq) >> 3)) & (KVB - 1))]);
+                acc_o[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, acc_o[nt], 0, 0, 0);
+            }
+        }
+    }
+    // ---- the four partials meet in LDS (each in its wave's image): row lq -> [D] un-normalised O (exp2 domain), m, l
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    float* part = reinterpret_cast<float*>(Vt);
+#pragma unroll
+    for (int nt = 0; nt < NDT; ++nt) *reinterpret_cast<f32x4*>(part + lq * PLD + nt * 16 + g * 4) = acc_o[nt];
+    if (g == 0) { part[lq * PLD + D] = m_run; part[lq * PLD + D + 1] = l_run; }
+    __syncthreads();
+    {   // 256 threads: row tid / 16, D / 16 consecutive columns each; the waves' partials are summed in wave order
+        const int row = tid >> 4, c0 = (tid & 15) * CPT;
+        const int Rr = rt * 16 + row;
+        if (Rr < G * a.m) {
+            const float* pw[PFX_WAVES];
+            float ms[PFX_WAVES], mm = -INFINITY;
+#pragma unroll
+            for (int w = 0; w < PFX_WAVES; ++w) {
+                pw[w] = reinterpret_cast<const float*>(reinterpret_cast<const bf16*>(pfx_smem) + w * PER_WAVE) + row * PLD;
+                ms[w] = pw[w][D];
+                mm = fmaxf(mm, ms[w]);
+            }
+            const float m_use = (mm == -INFINITY) ? 0.f : mm;
+            float l = 0.f, o[CPT];
+#pragma unroll
+            for (int cc = 0; cc < CPT; ++cc) o[cc] = 0.f;
+#pragma unroll
+            for (int w = 0; w < PFX_WAVES; ++w) {
+                const float wl = (ms[w] == -INFINITY) ? 0.f : exp2f(ms[w] - m_use);
+                l += pw[w][D + 1] * wl;
+#pragma unroll
+                for (int cc = 0; cc < CPT; ++cc) o[cc] += pw[w][c0 + cc] * wl;
+            }
+            const float inv = l > 0.f ? 1.0f / l : 0.f;        // (rows at or behind suf_len: l = 0 -> zeros)
+            const int hd = kh * G + Rr / a.m, qp = Rr % a.m;
+            bf16* op = O + (size_t)qp * a.o_rs + (size_t)hd * a.o_hs + c0;
+            const bf16x4 lo = {(bf16)(o[0] * inv), (bf16)(o[1] * inv), (bf16)(o[2] * inv), (bf16)(o[3] * inv)};
+            const bf16x4 hi = {(bf16)(o[4] * inv), (bf16)(o[5] * inv), (bf16)(o[6] * inv), (bf16)(o[7] * inv)};
+            *reinterpret_cast<bf16x4*>(op) = lo;
+            *reinterpret_cast<bf16x4*>(op + 4) = hi;
+        }
+    }
+}
+
+}  // namespace
+
+int ina_launch_attention_prefix(const void* Q, long q_ps, long q_rs, long q_hs, void* O, long o_ps, long o_rs, long o_hs, const void* Kc,
+                                const void* Vc, long c_ss, long c_rs, long c_hs, int n_slots, const void* Ks, const void* Vs, long s_ps, long s_rs,
+                                long s_hs, const int32_t* slot, const int32_t* pfx_len, const int32_t* suf_len, int P, int m, int H, int Hkv, int D,
+                                int max_pfx, float scale, hipStream_t stream) {
+    INA_REQUIRE(D == PFX_D, "attention_prefix: head dim %d (128 only)", D);
+    INA_REQUIRE(P >= 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "attention_prefix: bad P/H/Hkv (%d,%d,%d)", P, H, Hkv);
+    INA_REQUIRE(m >= 1 && m <= PFX_CHUNK, "attention_prefix: m=%d suffix rows (1 .. %d: the suffix is one key chunk)", m, PFX_CHUNK);
+    INA_REQUIRE(max_pfx >= 0 && n_slots >= 1, "attention_prefix: max_pfx=%d (>= 0), n_slots=%d (>= 1)", max_pfx, n_slots);
+    INA_REQUIRE(std::isfinite(scale), "attention_prefix: scale %g is not finite", (double)scale);
+    INA_REQUIRE(Q && O && Kc && Vc && Ks && Vs && slot && pfx_len && suf_len, "attention_prefix: null pointer (q, out, caches, suffix k / v and the three tables are required)");
+    INA_REQUIRE(q_ps % 8 == 0 && q_rs % 8 == 0 && q_hs % 8 == 0 && c_ss % 8 == 0 && c_rs % 8 == 0 && c_hs % 8 == 0 && s_ps % 8 == 0 && s_rs % 8 == 0 &&
+                    s_hs % 8 == 0 && o_ps % 4 == 0 && o_rs % 4 == 0 && o_hs % 4 == 0,
+                "attention_prefix: strides must keep 16-byte row alignment");
+    INA_REQUIRE(((uintptr_t)Q % 16) == 0 && ((uintptr_t)Kc % 16) == 0 && ((uintptr_t)Vc % 16) == 0 && ((uintptr_t)Ks % 16) == 0 &&
+                    ((uintptr_t)Vs % 16) == 0 && ((uintptr_t)O % 8) == 0,
+                "attention_prefix: misaligned pointer");
+    if (P == 0) return 0;
+    const int G = H / Hkv, rtiles = (G * m + 15) / 16;
+    INA_REQUIRE((long)P * rtiles <= 0x7fffffffL && Hkv <= 65535, "attention_prefix: grid of %d pairs x %d row tiles x %d KV heads", P, rtiles, Hkv);
+    PrefixArgs a;
+    a.Q = reinterpret_cast<const bf16*>(Q); a.O = reinterpret_cast<bf16*>(O);
+    a.Kc = reinterpret_cast<const bf16*>(Kc); a.Vc = reinterpret_cast<const bf16*>(Vc);
+    a.Ks = reinterpret_cast<const bf16*>(Ks); a.Vs = reinterpret_cast<const bf16*>(Vs);
+    a.slot = slot; a.pfx_len = pfx_len; a.suf_len = suf_len;
+    a.q_ps = q_ps; a.q_rs = q_rs; a.q_hs = q_hs; a.o_ps = o_ps; a.o_rs = o_rs; a.o_hs = o_hs;
+    a.c_ss = c_ss; a.c_rs = c_rs; a.c_hs = c_hs; a.s_ps = s_ps; a.s_rs = s_rs; a.s_hs = s_hs;
+    a.P = P; a.m = m; a.H = H; a.Hkv = Hkv; a.n_slots = n_slots; a.max_pfx = max_pfx; a.rtiles = rtiles; a.scale = scale;
+    // algorithmic bound: every row against max_pfx prefix keys + half the suffix; K / V of the prefix once per (pair, KV head) at most
+    const double keys = (double)max_pfx + 0.5 * (m + 1.0);
+    InaProfScope prof(INA_PROF_ATTN, 4.0 * P * H * (double)m * keys * D,
+                      2.0 * D * ((double)P * H * m * 2.0 + 2.0 * (double)P * Hkv * ((double)max_pfx + m)), stream);
+    constexpr size_t LDS = (size_t)PFX_WAVES * PFX_D * (PFX_CHUNK + 8) * sizeof(bf16);
+    static bool attr_done = false;
+    if (!attr_done) {
+        INA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_prefix_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(attn_prefix_kernel, dim3((unsigned)(P * rtiles), Hkv), dim3(PFX_WAVES * 64), LDS, stream, a);
+    INA_HIP_CHECK(hipGetLastError());
+    return 0;
+}

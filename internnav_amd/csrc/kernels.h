@@ -65,6 +65,10 @@ int ina_launch_goal_slots(void* Y, int ldy, int y_dtype, int L, int slot0, int n
                           int n_pixel, const float* pixel_w, const float* pixel_b, int ntok, int E, hipStream_t stream);   // goal_slots.hip
 int ina_launch_kv_copy(int to_engine, const int64_t* layer_base, int n_layers, const int64_t* seq, int n_seq, long engine_rows, long row_bytes,
                        long max_rows, hipStream_t stream);                                                                   // kv_copy.hip
+int ina_launch_attention_prefix(const void* Q, long q_ps, long q_rs, long q_hs, void* O, long o_ps, long o_rs, long o_hs, const void* Kc,
+                                const void* Vc, long c_ss, long c_rs, long c_hs, int n_slots, const void* Ks, const void* Vs, long s_ps, long s_rs,
+                                long s_hs, const int32_t* slot, const int32_t* pfx_len, const int32_t* suf_len, int P, int m, int H, int Hkv, int D,
+                                int max_pfx, float scale, hipStream_t stream);                                               // attention_prefix.hip
 int ina_launch_memory_gather(void* out, long out_env_stride, float* ring, const float* fresh, const float* blank, const float* pe,
                              const int32_t* env, const int32_t* head, const int32_t* count, int n, int max_envs, int M, int ntok, int C, int depth,
                              int stride, hipStream_t stream);                                                                // memory_gather.hip

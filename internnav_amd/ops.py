@@ -294,6 +294,44 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional
     return out
 
 
+ATTN_PREFIX_MAX_ROWS = 64     # suffix rows per pair of ops.attention_prefix (one 64-key chunk, csrc/attention_prefix.hip)
+
+
+def attention_prefix(q: torch.Tensor, k_suf: torch.Tensor, v_suf: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot: torch.Tensor,
+                     pfx_len: torch.Tensor, suf_len: torch.Tensor, out: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                     max_pfx: Optional[int] = None) -> torch.Tensor:
+    """causal self-attention of P short suffixes that also see a prefix kept once in a KV cache (ina_attention_prefix): query row i of pair p
+    (i < suf_len[p]) sees rows [0, pfx_len[p]) of cache slot slot[p] and suffix keys j <= i of pair p. Nothing is written to the cache.
+    q [P, m, H, 128], k_suf / v_suf [P, m, Hkv, 128] (equal strides), k_cache / v_cache [slots, S, Hkv, 128] (equal strides), all bf16 with a
+    contiguous last dim; slot / pfx_len / suf_len int32 [P] on the device. max_pfx (default S): the largest pfx_len (longer ones are clipped).
+    Rows i >= suf_len[p] come out as zeros, a slot outside the cache as NaN rows."""
+    assert q.dtype == k_suf.dtype == v_suf.dtype == k_cache.dtype == v_cache.dtype == torch.bfloat16
+    assert q.dim() == 4 and k_suf.dim() == 4 and k_cache.dim() == 4
+    P, m, H, D = q.shape
+    Hkv = k_suf.shape[2]
+    n_slots, S = k_cache.shape[0], k_cache.shape[1]
+    assert D == 128, f"attention_prefix: head dim {D} (128 only)"
+    assert 1 <= m <= ATTN_PREFIX_MAX_ROWS, f"attention_prefix: {m} suffix rows per pair (1 .. {ATTN_PREFIX_MAX_ROWS})"
+    assert Hkv > 0 and H % Hkv == 0, f"attention_prefix: {H} heads over {Hkv} KV heads"
+    assert k_suf.shape == (P, m, Hkv, D) and v_suf.shape == k_suf.shape and k_suf.stride() == v_suf.stride()
+    assert k_cache.shape == (n_slots, S, Hkv, D) and v_cache.shape == k_cache.shape and k_cache.stride() == v_cache.stride() and n_slots >= 1
+    if out is None:
+        out = torch.empty(P, m, H, D, dtype=torch.bfloat16, device=q.device)
+    assert out.shape == q.shape and out.dtype == torch.bfloat16
+    assert all(t.stride(-1) == 1 for t in (q, k_suf, v_suf, k_cache, v_cache, out))
+    for t in (slot, pfx_len, suf_len):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == P and t.device == q.device
+    max_pfx = S if max_pfx is None else int(max_pfx)
+    assert 0 <= max_pfx <= S, f"attention_prefix: max_pfx={max_pfx} outside the cache's {S} rows per slot"
+    rc = _lib.lib().ina_attention_prefix(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), out.data_ptr(), out.stride(0), out.stride(1), out.stride(2),
+                                         k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), n_slots,
+                                         k_suf.data_ptr(), v_suf.data_ptr(), k_suf.stride(0), k_suf.stride(1), k_suf.stride(2), slot.data_ptr(),
+                                         pfx_len.data_ptr(), suf_len.data_ptr(), P, m, H, Hkv, D, max_pfx,
+                                         float(scale) if scale is not None else float(D) ** -0.5, _stream())
+    _lib.check(rc, "attention_prefix")
+    return out
+
+
 def drop_params(p: float, seed: int):
     """(seed, threshold, scale) of the counter-based dropout mask: keep iff hash(seed, index) >= p * 2^32, kept values scaled by 1 / (1 - p)."""
     assert 0.0 < p < 1.0

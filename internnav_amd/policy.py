@@ -254,6 +254,64 @@ def score_row_plan(prompt_lens, answer_lens, slab_rows: int = SCORE_SLAB_ROWS):
     return S, rows, off, [(r0, min(r0 + slab_rows, R)) for r0 in range(0, R, slab_rows)]
 
 
+SCORE_SUFFIX_MAX_ROWS = 64  # candidate tokens a suffix pass runs per pair (ops.ATTN_PREFIX_MAX_ROWS): candidates of up to 65 tokens
+
+
+def score_prefix_plan(prompt_lens, answer_lens_per_prompt, max_rows: int, slab_rows: int = SCORE_SLAB_ROWS) -> dict:
+    """host plan of score_answers(share_prefix=True) for ONE group of prompts prefilled together (prompt b in cache slot b, right-padded to
+    S = the longest): answer_lens_per_prompt[b] = the token counts of prompt b's candidates. Pairs are numbered prompt-major.
+    Token 0 of a candidate is predicted by its prompt's last hidden row b * S + prompt_lens[b] - 1 (one gathered row per pair: the source index
+    repeats). Tokens 1 .. n - 1 are predicted by a suffix pass over the candidate's tokens 0 .. n - 2: pairs with n >= 2 are cut, in order, into
+    passes of P pairs x m rows (m = the longest of the pass, at most SCORE_SUFFIX_MAX_ROWS) with P * m <= max_rows; row j * m + i of a pass
+    predicts token i + 1 of its j-th pair. ->
+      S, pairs [(b, c)], off int64 [pairs + 1] (token i of pair q is value off[q] + i of the group's flat result), total = off[-1],
+      first_rows int32 / first_dst int64 / first_pair int64 [F] and first_slabs, the pairs with n >= 1,
+      passes: dicts of pair int64 [P], prompt int64 [P], m, suf_len int64 [P], rows int32 [R], dst int64 [R], slabs.
+    slabs = consecutive ranges of at most slab_rows gathered rows (one lm_head GEMM each)."""
+    pl = np.asarray(prompt_lens, dtype=np.int64).reshape(-1)
+    assert pl.size > 0 and len(answer_lens_per_prompt) == pl.size and int(pl.min()) >= 1 and slab_rows >= 1
+    pairs = [(b, c) for b in range(pl.size) for c in range(len(answer_lens_per_prompt[b]))]
+    al = np.asarray([int(answer_lens_per_prompt[b][c]) for b, c in pairs], dtype=np.int64)
+    assert al.size == 0 or int(al.min()) >= 0
+    if al.size and int(al.max()) - 1 > SCORE_SUFFIX_MAX_ROWS:
+        raise ValueError(f"a candidate of {int(al.max())} tokens exceeds the {SCORE_SUFFIX_MAX_ROWS + 1} tokens score_answers(share_prefix=True) "
+                         "scores behind a shared prompt: score it with share_prefix=False (one prefill per pair)")
+    longest = int(al.max()) if al.size else 0
+    assert max_rows >= max(1, longest - 1), f"max_rows={max_rows} cannot hold the {longest - 1} suffix rows of the longest candidate"
+    S = int(pl.max())
+    off = np.concatenate([[0], np.cumsum(al)]).astype(np.int64)
+    slabs = lambda R: [(r0, min(r0 + slab_rows, R)) for r0 in range(0, R, slab_rows)]
+    first = np.asarray([q for q in range(al.size) if al[q] >= 1], dtype=np.int64)
+    pb = np.asarray([b for b, _ in pairs], dtype=np.int64)
+    plan = dict(S=S, pairs=pairs, off=off, total=int(off[-1]), first_pair=first, first_rows=(pb[first] * S + pl[pb[first]] - 1).astype(np.int32),
+                first_dst=off[first], first_slabs=slabs(first.size), passes=[])
+    cur = []
+
+    def close():
+        if not cur:
+            return
+        q = np.asarray(cur, dtype=np.int64)
+        sl = al[q] - 1
+        m = int(sl.max())
+        rows = np.concatenate([j * m + np.arange(sl[j]) for j in range(q.size)]).astype(np.int32)
+        dst = np.concatenate([off[q[j]] + 1 + np.arange(sl[j]) for j in range(q.size)]).astype(np.int64)
+        plan["passes"].append(dict(pair=q, prompt=pb[q], m=m, suf_len=sl, rows=rows, dst=dst, slabs=slabs(rows.size)))
+        cur.clear()
+
+    m_cur = 0
+    for q in range(al.size):
+        if al[q] < 2:
+            continue
+        m_new = max(m_cur, int(al[q]) - 1)
+        if cur and (len(cur) + 1) * m_new > max_rows:
+            close()
+            m_new = int(al[q]) - 1
+        cur.append(q)
+        m_cur = m_new
+    close()
+    return plan
+
+
 class InternVLAN1ForCausalLM:
     """HF-style model object backed by the HIP engines (no nn.Module, no CPU fallback)."""
 
@@ -280,6 +338,7 @@ class InternVLAN1ForCausalLM:
         self.qwen = QwenVLEngine(weights, qwen_cfg, device, max_seqs=n_s2, max_seq_len=max_seq_len or cap_seq,
                                  max_patches=max_patches or n_s2 * cap_patches, w8_decode=w8_decode, token_logprobs=token_logprobs, max_decode=max_decode)
         self._score_logits = None       # fp32 [<= SCORE_SLAB_ROWS, vocab] of score_answers, allocated on first use
+        self.last_score = dict(prompt_prefills=0, images_encoded=0, suffix_rows=0, suffix_passes=0)      # counters of the last score_answers call
         if "nextdit" in system1:
             # the DiT's geometry (width, depth, heads, FFN width) is not in config.json - NextDiTCrossAttnConfig is constructed in code
             # (internvla_n1_arch.py:127-131) and its FFN width depends on the diffusers release (synthetic.lumina_ffn_width): read it off
@@ -459,7 +518,8 @@ class InternVLAN1ForCausalLM:
         pkv = self.qwen.kv_handle([ids_cpu[b, : int(keep[b])] for b in range(B)]) if use_cache else None
         return SimpleNamespace(sequences=seqs, past_key_values=pkv, **lp_out)
 
-    def score_answers(self, input_ids, answers, pixel_values=None, image_grid_thw=None, attention_mask=None) -> SimpleNamespace:
+    def score_answers(self, input_ids, answers, pixel_values=None, image_grid_thw=None, attention_mask=None, share_prefix: bool = False,
+                      max_suffix_rows: Optional[int] = None) -> SimpleNamespace:
         """Teacher-forced scoring of caller-supplied answers: how likely is each candidate given its prompt?
         input_ids int [B, S] (right-padded with attention_mask, as generate() takes them), answers: per prompt a list of candidate token-id
         lists (append EOS to a candidate to have EOS scored). -> token_logprobs: per prompt, per candidate an f32 tensor [len] with
@@ -470,7 +530,14 @@ class InternVLAN1ForCausalLM:
         Every (prompt, candidate) pair is one right-padded sequence of a normal prefill (images are encoded per pair: a prompt with four
         candidates runs the vision tower on its images four times), in groups of at most the engine's max_seqs pairs; the hidden rows that
         predict answer tokens are gathered, normed and run through lm_head into an fp32 [<= 256, vocab] buffer, and ops.logprob_rows reads the
-        target tokens' log-probabilities off it."""
+        target tokens' log-probabilities off it.
+        share_prefix=True (opt-in; the default path is unchanged): every prompt is prefilled ONCE (groups of at most max_seqs prompts, its images
+        encoded once), token 0 of each of its candidates is read off the prompt's last hidden row, and only the candidates' own tokens
+        0 .. n - 2 run through the stack as a suffix pass whose attention (ops.attention_prefix) reads the prompt's K/V in place in its cache
+        slot. Same result object; the values differ from the default path's by kernel rounding (other GEMM tiles, another attention kernel).
+        Candidates of more than 65 tokens raise ValueError (use the default path). max_suffix_rows: rows of one suffix pass (default: the
+        engine's row buffers).
+        `last_score` = dict(prompt_prefills, images_encoded, suffix_rows, suffix_passes) of the last call, either path."""
         q = self.qwen
         self._gen = None                                       # the cache slots are rewritten: generate_latents() must not continue an older generate()
         ids_cpu = input_ids.cpu().long()
@@ -494,6 +561,13 @@ class InternVLAN1ForCausalLM:
         vocab = q.cfg["vocab"]
         for b, cand in pairs:
             assert all(0 <= t < vocab for t in cand), "answer token outside the vocabulary"
+        if share_prefix:
+            longest = max((len(c) for _, c in pairs), default=0)
+            if longest - 1 > SCORE_SUFFIX_MAX_ROWS:             # before any launch
+                raise ValueError(f"score_answers(share_prefix=True) scores candidates of at most {SCORE_SUFFIX_MAX_ROWS + 1} tokens, got one of "
+                                 f"{longest}: score it with share_prefix=False (the per-pair path, one prefill per candidate)")
+            return self._score_shared_prefix(ids_cpu, plens, answers, pv_all, image_grid_thw, img_of, p_off, max_suffix_rows)
+        self.last_score = dict(prompt_prefills=0, images_encoded=0, suffix_rows=0, suffix_passes=0)
         out_lp = {}
         for g0 in range(0, len(pairs), q.B_max):
             grp = pairs[g0:g0 + q.B_max]
@@ -507,24 +581,13 @@ class InternVLAN1ForCausalLM:
             pv = torch.cat([pv_all[p_off[k]:p_off[k + 1]] for k in imgs], 0) if imgs else None
             grid = image_grid_thw[imgs] if imgs else None
             q.prefill(ids, pv, grid, seq_lens=pl + al)
+            self.last_score["prompt_prefills"] += len(grp)
+            self.last_score["images_encoded"] += len(imgs)
             R = int(off[-1])
             if R == 0:
                 continue
-            rows_d = torch.from_numpy(rows).to(self.device)
-            tgt = torch.tensor([t for _, c in grp for t in c], dtype=torch.int32, device=self.device)
             lp = torch.empty(R, dtype=torch.float32, device=self.device)
-            tok = torch.empty(R, dtype=torch.int32, device=self.device)
-            if self._score_logits is None:
-                self._score_logits = torch.empty(SCORE_SLAB_ROWS, vocab, dtype=torch.float32, device=self.device)
-                self._score_x = torch.empty(SCORE_SLAB_ROWS, q.H, dtype=torch.float32, device=self.device)
-                self._score_h = torch.empty(SCORE_SLAB_ROWS, q.H, dtype=torch.bfloat16, device=self.device)
-            for r0, r1 in slabs:
-                m = r1 - r0
-                x, h, logits = self._score_x[:m], self._score_h[:m], self._score_logits[:m]
-                ops.gather_rows(q.x[: len(grp) * S], x, src=rows_d[r0:r1])
-                ops.norm(x, q.norm_w, None, eps=1e-6, rms=True, out=h, rows=m)
-                ops.linear(h, q.lm_head, out=logits)
-                ops.logprob_rows(logits, tok[r0:r1], lp[r0:r1], target=tgt[r0:r1])
+            self._score_rows(q.x[: len(grp) * S], rows, slabs, [t for _, c in grp for t in c], lp)
             for r in range(len(grp)):
                 out_lp[g0 + r] = lp[off[r]:off[r + 1]]
         res_lp, res_len, res_sum, i = [], [], [], 0
@@ -535,6 +598,74 @@ class InternVLAN1ForCausalLM:
             res_len.append([int(t.numel()) for t in per])
             res_sum.append(torch.stack([t.sum() for t in per]) if per else torch.empty(0, dtype=torch.float32, device=self.device))
             i += n
+        return SimpleNamespace(token_logprobs=res_lp, lengths=res_len, sequences_logprob=res_sum)
+
+    def _score_rows(self, x_rows: torch.Tensor, rows: np.ndarray, slabs, targets, lp: torch.Tensor):
+        """gather rows of the residual stream, final norm, lm_head and the target tokens' log-probabilities, one slab at a time -> lp [len(rows)]"""
+        q, vocab = self.qwen, self.qwen.cfg["vocab"]
+        if self._score_logits is None:
+            self._score_logits = torch.empty(SCORE_SLAB_ROWS, vocab, dtype=torch.float32, device=self.device)
+            self._score_x = torch.empty(SCORE_SLAB_ROWS, q.H, dtype=torch.float32, device=self.device)
+            self._score_h = torch.empty(SCORE_SLAB_ROWS, q.H, dtype=torch.bfloat16, device=self.device)
+        rows_d = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(self.device)
+        tgt = torch.tensor(targets, dtype=torch.int32, device=self.device)
+        tok = torch.empty(len(targets), dtype=torch.int32, device=self.device)
+        for r0, r1 in slabs:
+            m = r1 - r0
+            x, h, logits = self._score_x[:m], self._score_h[:m], self._score_logits[:m]
+            ops.gather_rows(x_rows, x, src=rows_d[r0:r1])
+            ops.norm(x, q.norm_w, None, eps=1e-6, rms=True, out=h, rows=m)
+            ops.linear(h, q.lm_head, out=logits)
+            ops.logprob_rows(logits, tok[r0:r1], lp[r0:r1], target=tgt[r0:r1])
+
+    def _score_shared_prefix(self, ids_cpu, plens, answers, pv_all, image_grid_thw, img_of, p_off, max_suffix_rows) -> SimpleNamespace:
+        """score_answers(share_prefix=True): see there. Per group of prompts: one prefill, the first tokens off the prompts' last rows (before
+        the suffix pass reuses the residual buffer), then the suffix passes of `score_prefix_plan`."""
+        q = self.qwen
+        B = ids_cpu.shape[0]
+        max_rows = int(q.x.shape[0]) if max_suffix_rows is None else int(max_suffix_rows)
+        assert 1 <= max_rows <= q.x.shape[0], f"max_suffix_rows={max_rows} outside [1, {q.x.shape[0]}]"
+        self.last_score = dict(prompt_prefills=0, images_encoded=0, suffix_rows=0, suffix_passes=0)
+        empty = torch.empty(0, dtype=torch.float32, device=self.device)
+        res_lp, res_len, res_sum = [], [], []
+        for b0 in range(0, B, q.B_max):
+            grp = list(range(b0, min(b0 + q.B_max, B)))
+            pl = np.asarray([plens[b] for b in grp], dtype=np.int64)
+            cands = [[[int(t) for t in c] for c in answers[b]] for b in grp]
+            plan = score_prefix_plan(pl, [[len(c) for c in cs] for cs in cands], max_rows)
+            S = plan["S"]
+            ids = torch.zeros(len(grp), S, dtype=torch.long)
+            for r, b in enumerate(grp):
+                ids[r, : pl[r]] = ids_cpu[b, : pl[r]]
+            imgs = [k for b in grp for k in img_of[b]]
+            pv = torch.cat([pv_all[p_off[k]:p_off[k + 1]] for k in imgs], 0) if imgs else None
+            state = q.prefill(ids, pv, image_grid_thw[imgs] if imgs else None, seq_lens=pl)
+            self.last_score["prompt_prefills"] += len(grp)
+            self.last_score["images_encoded"] += len(imgs)
+            cand_of = [cands[r][c] for r, c in plan["pairs"]]
+            lp = torch.empty(plan["total"], dtype=torch.float32, device=self.device)
+            if plan["first_pair"].size:
+                first = torch.empty(plan["first_pair"].size, dtype=torch.float32, device=self.device)
+                self._score_rows(q.x[: len(grp) * S], plan["first_rows"], plan["first_slabs"], [cand_of[p][0] for p in plan["first_pair"]], first)
+                lp[torch.from_numpy(plan["first_dst"]).to(self.device)] = first
+            for ps in plan["passes"]:
+                P, m = ps["pair"].size, ps["m"]
+                toks = np.zeros((P, m), dtype=np.int64)
+                for j, p in enumerate(ps["pair"]):
+                    toks[j, : ps["suf_len"][j]] = cand_of[p][:-1]
+                x = q.suffix_pass(state, ps["prompt"], toks, ps["suf_len"])
+                part = torch.empty(ps["rows"].size, dtype=torch.float32, device=self.device)
+                self._score_rows(x, ps["rows"], ps["slabs"], [t for p in ps["pair"] for t in cand_of[p][1:]], part)
+                lp[torch.from_numpy(ps["dst"]).to(self.device)] = part
+                self.last_score["suffix_rows"] += P * m
+                self.last_score["suffix_passes"] += 1
+            off, k = plan["off"], 0
+            for r in range(len(grp)):
+                per = [lp[off[k + c]:off[k + c + 1]] if off[k + c + 1] > off[k + c] else empty for c in range(len(cands[r]))]
+                k += len(cands[r])
+                res_lp.append(per)
+                res_len.append([int(t.numel()) for t in per])
+                res_sum.append(torch.stack([t.sum() for t in per]) if per else empty)
         return SimpleNamespace(token_logprobs=res_lp, lengths=res_len, sequences_logprob=res_sum)
 
     def _import_past(self, input_ids, plens, pv, image_grid_thw, past, cached_image_embeds, tail):

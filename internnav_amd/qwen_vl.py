@@ -551,7 +551,13 @@ class QwenVLEngine:
         # (ina_attn_args.rope_cos): 5 launches per layer - q|k|v, attention, o, gate|up, down - in a chain that is launch / latency bound
         single = rows <= 16 and self.tap is None
         fused_norm = single and self.fuse_decode_norm
-        fuse_rope = single and self.fuse_decode_rope and ph.get("new_are_last", False) and ops.attention_rope_ok(S, ph["Lk"], nh, nkv, hd)
+        # suffix pass (ph["prefix"], `_suffix_phase`): B pairs x S candidate tokens behind prompts that stay in their cache slots - rope without
+        # the cache append, ops.attention_prefix in place of ops.attention; nothing of the cache is written
+        pfx = ph.get("prefix")
+        if pfx is not None:
+            k4 = qkv[:, nh * hd:(nh + nkv) * hd].view(B, S, nkv, hd)
+            v4 = qkv[:, (nh + nkv) * hd:].view(B, S, nkv, hd)
+        fuse_rope = pfx is None and single and self.fuse_decode_rope and ph.get("new_are_last", False) and ops.attention_rope_ok(S, ph["Lk"], nh, nkv, hd)
         if fuse_rope:
             kn4 = qkv[:, nh * hd:(nh + nkv) * hd].view(B, S, nkv, hd)
             vn4 = qkv[:, (nh + nkv) * hd:].view(B, S, nkv, hd)
@@ -565,12 +571,18 @@ class QwenVLEngine:
             else:
                 ops.norm(src, L["n1"], None, eps=1e-6, rms=True, out=h)
                 self._linear(h, L, "qkv_w", w8, bias=L["qkv_b"], out=qkv, w_frag=wf("qkv_wf"))
-            if not fuse_rope:
-                # m-rope on q (in place) and k, and the KV-cache append (rotated k | v -> cache row of every token) in ONE launch
-                ops.rope(qkv, cos, sin, heads=nh + nkv, D=hd, col0=0, rows=rows, kv_out=L["kv"], kv_dst=ph["rows"], kv_head0=nh, v_heads=nkv)
-            kv4 = L["kv"].view(self.B_max, Smax, 2, nkv, hd)[b0:b0 + B, : ph["Lk"]]
-            ops.attention(q4, kv4[:, :, 0], kv4[:, :, 1], causal=True, out=att.view(B, S, nh, hd), k_len=ph["k_len"],
-                          rope=(cos, sin, kn4, vn4) if fuse_rope else None)
+            if pfx is not None:
+                ops.rope(qkv, cos, sin, heads=nh + nkv, D=hd, col0=0, rows=rows)      # q and k in place: no cache append
+                kvc = L["kv"].view(self.B_max, Smax, 2, nkv, hd)
+                ops.attention_prefix(q4, k4, v4, kvc[:, :, 0], kvc[:, :, 1], pfx["slot"], pfx["pfx_len"], pfx["suf_len"],
+                                     out=att.view(B, S, nh, hd), max_pfx=pfx["max_pfx"])
+            else:
+                if not fuse_rope:
+                    # m-rope on q (in place) and k, and the KV-cache append (rotated k | v -> cache row of every token) in ONE launch
+                    ops.rope(qkv, cos, sin, heads=nh + nkv, D=hd, col0=0, rows=rows, kv_out=L["kv"], kv_dst=ph["rows"], kv_head0=nh, v_heads=nkv)
+                kv4 = L["kv"].view(self.B_max, Smax, 2, nkv, hd)[b0:b0 + B, : ph["Lk"]]
+                ops.attention(q4, kv4[:, :, 0], kv4[:, :, 1], causal=True, out=att.view(B, S, nh, hd), k_len=ph["k_len"],
+                              rope=(cos, sin, kn4, vn4) if fuse_rope else None)
             self._linear(att, L, "o_w", w8, residual=src, out=x)
             if fused_norm:
                 self._linear(x, L, "gu_w", w8, act="silu", glu=True, out=ff, prenorm=(L["n2"], 1e-6))
@@ -580,6 +592,40 @@ class QwenVLEngine:
             self._linear(ff, L, "down_w", w8, residual=x, out=x, w_frag=wf("down_wf"))
             if self.tap is not None:
                 self.tap("llm", li, x)
+
+    def _suffix_phase(self, slot, next_pos, pfx_len, suf_len, m: int) -> dict:
+        """host side of a suffix pass (`suffix_pass`): P pairs x m tokens; pair p continues the prompt in cache slot slot[p] (pfx_len[p] cached
+        tokens, next text position next_pos[p]) with suf_len[p] <= m tokens of its own. Positions are next_pos + i on all three m-rope axes -
+        what a decode would give the same tokens."""
+        dev = self.device
+        slot, pfx_len, suf_len = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (slot, pfx_len, suf_len))
+        P = slot.size
+        assert P >= 1 and pfx_len.size == P and suf_len.size == P and np.asarray(next_pos).size == P
+        if not 1 <= m <= ops.ATTN_PREFIX_MAX_ROWS:
+            raise ValueError(f"a suffix pass runs 1 .. {ops.ATTN_PREFIX_MAX_ROWS} tokens per pair, got {m}")
+        if P * m > self.x.shape[0]:
+            raise CapacityError(f"suffix pass of {P} x {m} tokens exceeds the engine's {self.x.shape[0]} buffer rows")
+        assert int(slot.min()) >= 0 and int(slot.max()) < self.B_max and int(pfx_len.min()) >= 0 and int(pfx_len.max()) <= self.S_max
+        assert int(suf_len.min()) >= 0 and int(suf_len.max()) <= m
+        pos = (np.asarray(next_pos, dtype=np.int64).reshape(-1, 1) + np.arange(m)[None]).reshape(1, P * m)
+        i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(dev)
+        return dict(B=P, S=m, pos=i32(np.broadcast_to(pos, (3, P * m))), b0=0, r0=0,
+                    prefix=dict(slot=i32(slot), pfx_len=i32(pfx_len), suf_len=i32(suf_len), max_pfx=int(pfx_len.max())))
+
+    def suffix_pass(self, state: dict, prompt_of, tokens, suf_len) -> torch.Tensor:
+        """teacher-forced continuation of prefilled prompts WITHOUT touching their cache slots: pair p runs tokens[p, :suf_len[p]] (int [P, m],
+        right-padded) behind prompt prompt_of[p] of `state` (what `prefill` returned). -> x f32 [P * m, H] (a view of the engine's residual
+        buffer: row p * m + i is the last hidden state at suffix position i; the prompts' own rows in that buffer are overwritten)."""
+        tokens = np.asarray(tokens, dtype=np.int64)
+        P, m = tokens.shape
+        prompt_of = np.asarray(prompt_of, dtype=np.int64).reshape(-1)
+        assert prompt_of.size == P and int(prompt_of.min()) >= 0 and int(prompt_of.max()) < state["B"]
+        lens = state.get("lens")
+        pl = np.full(state["B"], state["S"], dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64)
+        ph = self._suffix_phase(prompt_of, np.asarray(state["next_pos"])[prompt_of], pl[prompt_of], suf_len, m)
+        ops.gather_rows(self.embed, self.x_in, src=torch.from_numpy(tokens.reshape(-1).astype(np.int32)).to(self.device), rows=P * m)
+        self._layers(ph)
+        return self.x[: P * m]
 
     def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None, penalty: Optional[float] = None, col: int = 0):
         """final RMSNorm + lm_head on ONE row per sequence, greedy argmax on the device. row_in_seq: the same row for every sequence,
