@@ -56,7 +56,7 @@ int ina_workspace_retired(void);
 int ina_prof_enable(int on);
 int ina_prof_read(int kind, double* ms_total, int64_t* launches, double* flops, double* bytes);
 /* the same tally restricted to one kernel of the class: sub = GEMM tile config id (18 = gemm_bf16_pp_kernel<256,256,4>, 21 = <192,256,4>,
- * 22 = gemm_bf16_glds_kernel<128,128,2,2,1>, 33 = gemm_bf16_glds_kernel<256,256,4,4,2>, 11 / 14 / 26 / 27 other LDS-DMA tiles, 1-5 gemm_bf16_nt_kernel tiles, 34 / 35 = gemm_bf16_rowpanel_kernel<8|4 waves>, 39 = gemm_bf16_w4_kernel<256> (four-wave 256x256 tile), 40 = gemm_bf16_w4p_kernel<256> (the same tile on fragment-ordered weights), 42 = dit_rowchain_kernel, 43 = gemm_dw_kernel; in class 4: 48 = the fp8-weight kernels of ina_gemm_w8) */
+ * 22 = gemm_bf16_glds_kernel<128,128,2,2,1>, 33 = gemm_bf16_glds_kernel<256,256,4,4,2>, 11 / 14 / 26 / 27 other LDS-DMA tiles, 1-5 gemm_bf16_nt_kernel tiles, 34 / 35 = gemm_bf16_rowpanel_kernel<8|4 waves>, 39 = gemm_bf16_w4_kernel<256> (four-wave 256x256 tile), 40 = gemm_bf16_w4p_kernel<256> (the same tile on fragment-ordered weights), 42 = dit_rowchain_kernel, 43 = gemm_dw_kernel; in class 4: 48 = the fp8-weight kernels of ina_gemm_w8, 49 = the MXFP4-weight kernels of ina_gemm_mx4) */
 int ina_prof_read_sub(int kind, int sub, double* ms_total, int64_t* launches, double* flops, double* bytes);
 
 /* ---- C[M,N] = epilogue(A[M,K] . W[N,K]^T): replaces every nn.Linear / patch-embed conv on the path
@@ -110,6 +110,20 @@ int ina_gemm_bf16(const ina_gemm_args* args, void* stream);
  * with M > 16 / K > 4096 / N < 256, and the glu / R / colscale / act combinations ina_gemm_bf16 refuses.
  * Profiler tally: class 4 (weight streaming), sub 48, with N * K + N weight bytes. */
 int ina_gemm_w8(const ina_gemm_args* args, const void* W8, const int8_t* wexp, void* stream);
+/* The same weight-streaming kernels on MXFP4 weights (OCP microscaling): W4 holds e2m1 elements, two per byte, and wscale one e8m0 byte
+ * (127 + e, |e| <= 64, never 0xFF) per block of 32 consecutive k; the weight is q[n,k] * 2^e[n,k/32] with |q| in {0, .5, 1, 1.5, 2, 3, 4, 6},
+ * exactly a bf16 number. The result is, bit for bit, ina_gemm_bf16's weight-streaming result (kernel 32 / 30) on those dequantised bf16
+ * weights: same K decomposition and summation order; the block scale is applied inside the (exact) e2m1 -> bf16 conversion, so nothing is
+ * left for the epilogue. 0.53 bytes per weight.
+ * Packed row layout (K % 128 == 0): element k = step * 128 + s * 32 + g * 8 + j (s < 4, g < 4, j < 8) is nibble j (bits 4j .. 4j + 3) of the
+ * little-endian dword g * 4 + s of the 64-byte K step `step` of its row; rows are ldw BYTES apart (ldw >= K / 2, a multiple of 16). Scales
+ * in natural order: row n, block b at wscale[n * (K / 32) + b], contiguous, 4-byte aligned. args->W is ignored; every other field means
+ * what it means for ina_gemm_bf16.
+ * Refused (non-zero, ina_last_error; checked before any HIP call): null pointers, M > 64, K % 128 != 0, ldw < K / 2 or not a multiple of
+ * 16, batch > 1, seg_stats, Wp, force_cfg > 0, norm_gamma with M > 16 / K > 4096 / N < 256, and the glu / R / colscale / act combinations
+ * ina_gemm_bf16 refuses.
+ * Profiler tally: class 4 (weight streaming), sub 49, with N * K / 2 + N * K / 32 weight bytes. */
+int ina_gemm_mx4(const ina_gemm_args* args, const void* W4, const void* wscale, void* stream);
 /* W bf16 [N,K] (row stride ldw) -> Wp bf16 [N*K]: fragment (n / 16, k / 32) is one contiguous KiB, element (n, k) at
  * ((n / 16) * (K / 32) + k / 32) * 512 + ((k % 32) / 8 * 16 + n % 16) * 8 + k % 8. Done once per weight at load time. */
 int ina_gemm_preshuffle(const void* W, void* Wp, int32_t N, int32_t K, int64_t ldw, void* stream);

@@ -280,6 +280,7 @@ SYMBOLS = {
     "ina_device_check": (C.c_int, [C.c_char_p, C.c_int]),
     "ina_gemm_bf16": (C.c_int, [C.POINTER(GemmArgs), c_void_p]),
     "ina_gemm_w8": (C.c_int, [C.POINTER(GemmArgs), c_void_p, c_void_p, c_void_p]),
+    "ina_gemm_mx4": (C.c_int, [C.POINTER(GemmArgs), c_void_p, c_void_p, c_void_p]),
     "ina_gemm_select": (C.c_int, [C.POINTER(GemmArgs), C.POINTER(C.c_int)]),
     "ina_gemm_preshuffle": (C.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p]),
     "ina_attention_bf16": (C.c_int, [C.POINTER(AttnArgs), c_void_p]),

@@ -164,6 +164,11 @@ int ina_gemm_w8(const ina_gemm_args* args, const void* W8, const int8_t* wexp, v
     return ina_launch_gemm_w8(*args, W8, wexp, reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_gemm_mx4(const ina_gemm_args* args, const void* W4, const void* wscale, void* stream) {
+    INA_REQUIRE(args != nullptr, "gemm_mx4: null args");
+    return ina_launch_gemm_mx4(*args, W4, wscale, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_gemm_preshuffle(const void* W, void* Wp, int32_t N, int32_t K, int64_t ldw, void* stream) {
     return ina_launch_gemm_preshuffle(W, Wp, N, K, (long)ldw, reinterpret_cast<hipStream_t>(stream));
 }

@@ -187,10 +187,17 @@ def linear_w8(x: torch.Tensor, w8: torch.Tensor, wexp: torch.Tensor, bias: Optio
     assert (x.dtype == torch.bfloat16 or prenorm is not None) and w8.dtype == torch.uint8 and wexp.dtype == torch.int8
     assert w8.dim() == 2 and w8.stride(1) == 1 and wexp.is_contiguous() and wexp.numel() == w8.shape[0]
     N, K = w8.shape
+    return _linear_packed("ina_gemm_w8", "gemm_w8", x, w8, wexp, N, K, bias, act, colscale, residual, out, out_dtype, glu, rowscale, rowscale_div, prenorm)
+
+
+def _linear_packed(entry: str, what: str, x, wq, wside, N: int, K: int, bias, act, colscale, residual, out, out_dtype, glu, rowscale, rowscale_div,
+                   prenorm) -> torch.Tensor:
+    """the call of a quantised-weight form of the weight-streaming GEMMs (ina_gemm_w8 / ina_gemm_mx4): wq = the packed weight rows (row
+    pitch in bytes = stride(0)), wside = its exponents / block scales; every other operand as in `linear`"""
     n_out = N // 2 if glu else N
     lead = x.shape[:-1]
     x2 = _as2d(x)
-    assert x2.dim() == 2 and x.shape[-1] == K, f"K mismatch {tuple(w8.shape)} vs {tuple(x.shape)}"
+    assert x2.dim() == 2 and x.shape[-1] == K, f"K mismatch {(N, K)} vs {tuple(x.shape)}"
     M = x2.shape[0]
     if out is None:
         out = torch.empty(*lead, n_out, dtype=out_dtype, device=x.device)
@@ -204,7 +211,7 @@ def linear_w8(x: torch.Tensor, w8: torch.Tensor, wexp: torch.Tensor, bias: Optio
         r2 = _as2d(residual)
         assert r2.shape == (M, n_out)
         a.R, a.ldr, a.res_dtype = r2.data_ptr(), r2.stride(0), _DT[r2.dtype]
-    a.ldw = w8.stride(0)
+    a.ldw = wq.stride(0)
     a.bias, a.colscale, a.rowscale = _ptr(_f32(bias)), _ptr(_f32(colscale)), _ptr(_f32(rowscale))
     a.M, a.N, a.K = M, N, K
     a.act = ACT[act] if not isinstance(act, int) else act
@@ -215,8 +222,68 @@ def linear_w8(x: torch.Tensor, w8: torch.Tensor, wexp: torch.Tensor, bias: Optio
         gamma, eps = prenorm
         assert x.dtype in (torch.bfloat16, torch.float32) and gamma.dtype == torch.float32 and gamma.is_contiguous() and gamma.numel() == K
         a.norm_gamma, a.norm_eps, a.a_dtype = gamma.data_ptr(), float(eps), _DT[x.dtype]
-    _lib.check(_lib.lib().ina_gemm_w8(C.byref(a), w8.data_ptr(), wexp.data_ptr(), _stream()), "gemm_w8")
+    _lib.check(getattr(_lib.lib(), entry)(C.byref(a), wq.data_ptr(), wside.data_ptr(), _stream()), what)
     return out
+
+
+# ---- MXFP4 weights of the weight-streaming GEMMs (csrc/gemm_skinny_mx4.hip): OCP e2m1 elements, two per byte, + an e8m0 scale per 32 k
+MX4_BLOCK = 32
+# e2m1 codes 0 .. 7 stand for |value| 0, 0.5, 1, 1.5, 2, 3, 4, 6; bit 3 of a code is the sign
+
+
+def mx4_pack(q: torch.Tensor) -> torch.Tensor:
+    """e2m1 codes uint8 [N, K] (one code 0 .. 15 per element, natural k order, K % 128 == 0) -> the kernels' row layout uint8 [N, K / 2]:
+    element k = step * 128 + s * 32 + g * 8 + j (MFMA step s, lane group g, lane element j) is nibble j (bits 4j .. 4j + 3) of the
+    little-endian dword g * 4 + s of the row's 64-byte K step, i.e. byte step * 64 + (g * 4 + s) * 4 + j // 2, low nibble for even j. A
+    lane's four fragments of a K step are 16 contiguous bytes, the four lane groups of a row 64."""
+    assert q.dtype == torch.uint8 and q.dim() == 2 and q.shape[1] % 128 == 0, "mx4 layout: uint8 codes [N, K] with K % 128 == 0"
+    N, K = q.shape
+    c = q.reshape(N, K // 128, 4, 4, 4, 2).transpose(2, 3)          # [N, step, g, s, j // 2, j % 2]
+    return (c[..., 0] | (c[..., 1] << 4)).reshape(N, K // 2).contiguous()
+
+
+def mx4_unpack(p: torch.Tensor) -> torch.Tensor:
+    """inverse of mx4_pack: packed uint8 [N, K / 2] -> codes uint8 [N, K] in natural k order"""
+    assert p.dtype == torch.uint8 and p.dim() == 2 and p.shape[1] % 64 == 0, "mx4 layout: packed uint8 [N, K / 2] with K % 128 == 0"
+    N, K = p.shape[0], p.shape[1] * 2
+    b = p.reshape(N, K // 128, 4, 4, 4)                              # [N, step, g, s, j // 2]
+    return torch.stack([b & 15, b >> 4], dim=-1).transpose(2, 3).reshape(N, K).contiguous()
+
+
+def mx4_quantize(w: torch.Tensor):
+    """w bf16 [N, K] (K % 128 == 0) -> (w4 uint8 [N, K / 2] packed e2m1, wscale uint8 [N, K / 32] e8m0 bytes 127 + e, w_deq bf16 [N, K]).
+
+    OCP microscaling, round to nearest: a block of 32 consecutive k shares e = floor(log2(amax)) - 2 (the block's amax lands in [4, 8),
+    e2m1's top binade), clamped to [-64, 64]; an element is w / 2^e rounded to nearest-even onto {0, .5, 1, 1.5, 2, 3, 4, 6} and
+    saturated at 6 (an amax in (6, 8) * 2^e does). A block whose elements all round to zero - an all-zero block, or one far below the
+    clamp - stores e = 0. w_deq = q * 2^e is exact in bf16 - it is the model the MXFP4 kernels compute - and mx4_quantize(w_deq)
+    returns the same three tensors."""
+    assert w.dtype == torch.bfloat16 and w.dim() == 2 and w.shape[1] % 128 == 0, "mx4_quantize: bf16 [N, K] with K % 128 == 0"
+    N, K = w.shape
+    wf = w.float().reshape(N, K // MX4_BLOCK, MX4_BLOCK)
+    amax = wf.abs().amax(dim=2)
+    _, x = torch.frexp(amax)                      # amax = m * 2^x, m in [0.5, 1): floor(log2(amax)) = x - 1, exactly
+    e = torch.where(amax == 0, torch.zeros_like(x), x - 3).clamp(-W8_EXP_RANGE, W8_EXP_RANGE).to(torch.int32)
+    a = torch.ldexp(wf.abs(), (-e)[..., None])
+    # the e2m1 grid has steps of 0.5 below 2, 1 below 4 and 2 above; torch.round rounds halves to even, which is the even code here
+    r = torch.where(a < 2, torch.round(a * 2) * 0.5, torch.where(a < 4, torch.round(a), (torch.round(a * 0.5) * 2).clamp(max=6.0)))
+    e = torch.where((r == 0).all(dim=2), torch.zeros_like(e), e)
+    code = torch.where(r < 2, r * 2, torch.where(r < 4, r + 2, r * 0.5 + 4)).to(torch.uint8) | (torch.signbit(wf).to(torch.uint8) << 3)
+    w_deq = torch.ldexp(torch.where(torch.signbit(wf), -r, r), e[..., None]).to(torch.bfloat16).reshape(N, K)
+    return mx4_pack(code.reshape(N, K)), (e + 127).to(torch.uint8).contiguous(), w_deq.contiguous()
+
+
+def linear_mx4(x: torch.Tensor, w4: torch.Tensor, wscale: torch.Tensor, bias: Optional[torch.Tensor] = None, act=None,
+               colscale: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None, out_dtype=torch.bfloat16, glu: bool = False,
+               rowscale: Optional[torch.Tensor] = None, rowscale_div: int = 1, prenorm=None) -> torch.Tensor:
+    """`linear` on MXFP4 weights for at most 64 rows (prenorm: 16): w4 uint8 [N, K / 2] packed (mx4_quantize / mx4_pack; rows may be strided),
+    wscale uint8 [N, K / 32] contiguous. Bit for bit the weight-streaming result of linear(x, w_deq, ...) on the dequantised weights, at
+    0.27 of the weight bytes."""
+    assert (x.dtype == torch.bfloat16 or prenorm is not None) and w4.dtype == torch.uint8 and wscale.dtype == torch.uint8
+    assert w4.dim() == 2 and w4.stride(1) == 1 and wscale.is_contiguous() and wscale.shape == (w4.shape[0], w4.shape[1] // 16)
+    N, K = w4.shape[0], w4.shape[1] * 2
+    return _linear_packed("ina_gemm_mx4", "gemm_mx4", x, w4, wscale, N, K, bias, act, colscale, residual, out, out_dtype, glu, rowscale, rowscale_div, prenorm)
 
 
 def attention_rope_ok(Lq: int, Lk: int, H: int, Hkv: int, D: int) -> bool:

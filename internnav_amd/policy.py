@@ -319,7 +319,8 @@ class InternVLAN1ForCausalLM:
                  device="cuda:0", max_envs: int = 16, max_seq_len: Optional[int] = None, max_patches: Optional[int] = None,
                  max_s2_seqs: Optional[int] = None, num_history: int = 8, resize_w: int = 384, resize_h: int = 384,
                  cam_w: int = 640, cam_h: int = 480, w8_decode: bool = False, generation_config: Optional[dict] = None,
-                 ignore_generation_config: bool = False, token_logprobs: bool = False, max_decode: int = 128):
+                 ignore_generation_config: bool = False, token_logprobs: bool = False, max_decode: int = 128,
+                 mx4_decode: bool = False):
         """Engine capacity defaults to the longest prompt the reference's harness can build for (num_history, resize, camera size):
         see `s2_capacity`; exceeding it raises `CapacityError` (never a silent STOP).
         token_logprobs (opt-in): the System-2 engine keeps the log-probability and top-2 margin of every greedy token
@@ -336,7 +337,8 @@ class InternVLAN1ForCausalLM:
         n_s2 = max_s2_seqs or max_envs   # System-2 runs on micro-batches of the envs whose plan expired (agent / bench schedule)
         cap_seq, cap_patches = s2_capacity(num_history, resize_w, resize_h, cam_w, cam_h, n_query=qwen_cfg["n_query"])
         self.qwen = QwenVLEngine(weights, qwen_cfg, device, max_seqs=n_s2, max_seq_len=max_seq_len or cap_seq,
-                                 max_patches=max_patches or n_s2 * cap_patches, w8_decode=w8_decode, token_logprobs=token_logprobs, max_decode=max_decode)
+                                 max_patches=max_patches or n_s2 * cap_patches, w8_decode=w8_decode, token_logprobs=token_logprobs, max_decode=max_decode,
+                                 mx4_decode=mx4_decode)
         self._score_logits = None       # fp32 [<= SCORE_SLAB_ROWS, vocab] of score_answers, allocated on first use
         self.last_score = dict(prompt_prefills=0, images_encoded=0, suffix_rows=0, suffix_passes=0)      # counters of the last score_answers call
         if "nextdit" in system1:
@@ -888,7 +890,7 @@ class InternVLAN1Net:
     def _load(cls, ms: dict):
         """model + processor for a model_settings dict, loaded once per (checkpoint, device) and shared afterwards."""
         key = (str(ms["model_path"]), str(ms.get("device", "cuda:0")), bool(ms.get("w8_decode", False)), bool(ms.get("ignore_generation_config", False)),
-               bool(ms.get("token_logprobs", False)))
+               bool(ms.get("token_logprobs", False)), bool(ms.get("mx4_decode", False)))
         if key not in cls._shared:
             n_env = int(ms.get("env_num", 1) or 1)
             model = InternVLAN1ForCausalLM.from_pretrained(
@@ -897,6 +899,7 @@ class InternVLAN1Net:
                 resize_w=ms.get("resize_w", 384), resize_h=ms.get("resize_h", 384), cam_w=ms.get("width", 640), cam_h=ms.get("height", 480),
                 w8_decode=bool(ms.get("w8_decode", False)),      # System-2 single-token passes on FP8 weights (QwenVLEngine(w8_decode=True))
                 ignore_generation_config=bool(ms.get("ignore_generation_config", False)),
+                mx4_decode=bool(ms.get("mx4_decode", False)),    # ... on MXFP4 weights (QwenVLEngine(mx4_decode=True)); not both
                 token_logprobs=bool(ms.get("token_logprobs", False)))   # per-token log-probabilities of System-2 answers (S2Output.answer_logprob)
             cls._shared[key] = (model.eval(), cls.load_processor(ms["model_path"]))
         return cls._shared[key]

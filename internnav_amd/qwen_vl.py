@@ -256,6 +256,24 @@ def w8_roundtrip_state_dict(sd, cfg: dict) -> dict:
     return out
 
 
+def mx4_roundtrip_state_dict(sd, cfg: dict) -> dict:
+    """the checkpoint an engine built with mx4_decode=True computes: q / k / v / o / gate / up / down of every decoder layer replaced by
+    their MXFP4 round trip (ops.mx4_quantize of the bf16 weight: the blocks run along K inside one output row, so fusing or interleaving rows
+    afterwards changes nothing) and lm_head by its e4m3 * 2^e round trip (ops.w8_quantize); every other tensor is passed through. For tests,
+    and for evaluating the quantised model elsewhere."""
+    names = {f"model.layers.{i}.{k}" for i in range(cfg["t_layers"]) for k in W8_DECODER_KEYS}
+    out = {}
+    for k in sd.keys():
+        v = sd[k]
+        if k in names:
+            out[k] = ops.mx4_quantize(v.to(torch.bfloat16).contiguous())[2].to(v.dtype)
+        elif k == "lm_head.weight":
+            out[k] = ops.w8_quantize(v.to(torch.bfloat16).contiguous())[2].to(v.dtype)
+        else:
+            out[k] = v
+    return out
+
+
 def _interleave16(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     n, k = a.shape
     return torch.stack([a.view(n // 16, 16, k), b.view(n // 16, 16, k)], dim=1).reshape(2 * n, k).contiguous()
@@ -269,10 +287,13 @@ class QwenVLEngine:
     """weights: mapping key -> tensor (a state dict, or a lazy provider that materialises tensors on the device)."""
 
     def __init__(self, weights, cfg: dict, device="cuda:0", max_seqs: int = 16, max_seq_len: int = 1024, max_patches: int = 16 * 3136,
-                 frag_weights: Optional[bool] = None, w8_decode: bool = False, token_logprobs: bool = False, max_decode: int = 128):
+                 frag_weights: Optional[bool] = None, w8_decode: bool = False, token_logprobs: bool = False, max_decode: int = 128,
+                 mx4_decode: bool = False):
         """token_logprobs (opt-in, fixed for the engine's life: captured graphs and cached models are of one setting): every greedy selection
         also writes the log-probability and the top-2 margin of the chosen token (ops.logprob_rows IN PLACE of the argmax launch: same launch
         count, same tokens) into per-step device buffers for up to max_decode answer tokens; read them with `last_logprobs`."""
+        if w8_decode and mx4_decode:
+            raise ValueError("w8_decode and mx4_decode are two roundings of the same weights: choose one")
         dev = torch.device(device)
         bf, f32 = torch.bfloat16, torch.float32
         self.cfg, self.device = cfg, dev
@@ -354,10 +375,15 @@ class QwenVLEngine:
         # w8_decode: the decoder projections and lm_head rounded to e4m3 * 2^e per output row (ops.w8_quantize). The bf16 tensors then hold the
         # dequantised values - the model every pass computes - and the GEMMs of at most SKINNY_GEMM_MAX_ROWS rows stream the fp8 bytes instead
         # (ops.linear_w8: half the weight bytes, the same bits as the bf16 weight-streaming kernels on the dequantised weights)
+        # mx4_decode: the same for the decoder projections in MXFP4 (ops.mx4_quantize: e2m1 elements, an e8m0 scale per 32 k; ops.linear_mx4
+        # streams 0.27 of the bf16 bytes, same bits on the dequantised weights); lm_head, the most sensitive layer, goes the e4m3 way
         self.w8_decode = False
+        self.mx4_decode = False
         self.lm_head8 = None
         if w8_decode:
             self.refresh_w8_weights()          # (rebuilds the fragment-ordered copies from the dequantised weights)
+        elif mx4_decode:
+            self.refresh_mx4_weights()         # (likewise)
         elif self.frag_weights:
             self.refresh_frag_weights()
         self.latent_q = W["model.latent_queries"].to(device=dev, dtype=bf).reshape(-1, H).contiguous()
@@ -491,6 +517,8 @@ class QwenVLEngine:
         with the dequantised values (twins and the prefill keep reading them; quantising them again changes nothing), the packed fp8 bytes
         and the exponents are kept beside them (+ 7 GB at the 7B geometry) and the fragment-ordered copies are rebuilt. Vision tower,
         embeddings, norms and biases are untouched."""
+        if self.mx4_decode:
+            raise ValueError("refresh_w8_weights on an mx4_decode engine: drop_mx4_weights() first (the weights would be rounded twice)")
         for L in self.layers:
             for k in self.W8_LAYER_WEIGHTS:
                 w8, e, wd = ops.w8_quantize(L[k])
@@ -511,10 +539,44 @@ class QwenVLEngine:
             for k in self.W8_LAYER_WEIGHTS:
                 L.pop(k + "8", None)
 
-    def _linear(self, x, L: dict, k: str, w8: bool, **kw):
-        """one decoder projection: the fp8 weight stream where this pass uses it (same bits), else the bf16 kernels"""
-        if w8:
+    def refresh_mx4_weights(self):
+        """(re)quantise q|k|v, o, gate|up, down of every decoder layer to MXFP4 (e2m1 elements, one e8m0 scale per 32 consecutive k) and
+        lm_head to e4m3 with a power-of-two scale per output row - at load (mx4_decode=True), and after anything that replaces or updates
+        one of these weights in place. The fused / interleaved tensors are quantised as they stand: a block lies inside one output row, so
+        the rounding commutes with every permutation of rows. The bf16 tensors are overwritten IN PLACE with the dequantised values (twins
+        and the prefill keep reading them; quantising them again changes nothing), the packed bytes and scales are kept beside them (+ 3.5 GB
+        and + 0.55 GB for lm_head at the 7B geometry) and the fragment-ordered copies are rebuilt. Vision tower, embeddings, norms and
+        biases are untouched."""
+        if self.w8_decode:
+            raise ValueError("refresh_mx4_weights on a w8_decode engine: drop_w8_weights() first (the weights would be rounded twice)")
+        for L in self.layers:
+            for k in self.W8_LAYER_WEIGHTS:
+                w4, sc, wd = ops.mx4_quantize(L[k])
+                L[k].copy_(wd)
+                L[k + "4"] = (w4, sc)
+        w8, e, wd = ops.w8_quantize(self.lm_head)
+        self.lm_head.copy_(wd)
+        self.lm_head8 = (w8, e)
+        self.mx4_decode = True
+        if self.frag_weights:
+            self.refresh_frag_weights()
+
+    def drop_mx4_weights(self):
+        """release the MXFP4 copies and lm_head's fp8 copy: the single-token passes stream the (dequantised) bf16 weights again - the same
+        model, the same bits"""
+        self.mx4_decode = False
+        self.lm_head8 = None
+        for L in self.layers:
+            for k in self.W8_LAYER_WEIGHTS:
+                L.pop(k + "4", None)
+
+    def _linear(self, x, L: dict, k: str, quant, **kw):
+        """one decoder projection: the quantised weight stream this pass uses (quant "8": fp8, "4": MXFP4; same bits as the bf16 kernels on
+        the dequantised weights), else (None / False) the bf16 kernels"""
+        if quant:
             kw.pop("w_frag", None)
+            if quant == "4":
+                return ops.linear_mx4(x, *L[k + "4"], **kw)
             return ops.linear_w8(x, *L[k + "8"], **kw)
         return ops.linear(x, L[k], **kw)
 
@@ -562,15 +624,16 @@ class QwenVLEngine:
             kn4 = qkv[:, nh * hd:(nh + nkv) * hd].view(B, S, nkv, hd)
             vn4 = qkv[:, (nh + nkv) * hd:].view(B, S, nkv, hd)
         # w8_decode: every GEMM of this pass that would run the bf16 weight-streaming kernels reads the fp8 copy instead
-        w8 = self.w8_decode and rows <= SKINNY_GEMM_MAX_ROWS
+        # (mx4_decode: the MXFP4 copy)
+        quant = ("8" if self.w8_decode else "4" if self.mx4_decode else None) if rows <= SKINNY_GEMM_MAX_ROWS else None
         for li, L in enumerate(self.layers):
             src = x_in if li == 0 else x
             wf = (lambda k, L=L: L.get(k)) if (self.frag_weights and rows > SKINNY_GEMM_MAX_ROWS) else (lambda k: None)
             if fused_norm:
-                self._linear(src, L, "qkv_w", w8, bias=L["qkv_b"], out=qkv, prenorm=(L["n1"], 1e-6))
+                self._linear(src, L, "qkv_w", quant, bias=L["qkv_b"], out=qkv, prenorm=(L["n1"], 1e-6))
             else:
                 ops.norm(src, L["n1"], None, eps=1e-6, rms=True, out=h)
-                self._linear(h, L, "qkv_w", w8, bias=L["qkv_b"], out=qkv, w_frag=wf("qkv_wf"))
+                self._linear(h, L, "qkv_w", quant, bias=L["qkv_b"], out=qkv, w_frag=wf("qkv_wf"))
             if pfx is not None:
                 ops.rope(qkv, cos, sin, heads=nh + nkv, D=hd, col0=0, rows=rows)      # q and k in place: no cache append
                 kvc = L["kv"].view(self.B_max, Smax, 2, nkv, hd)
@@ -583,13 +646,13 @@ class QwenVLEngine:
                 kv4 = L["kv"].view(self.B_max, Smax, 2, nkv, hd)[b0:b0 + B, : ph["Lk"]]
                 ops.attention(q4, kv4[:, :, 0], kv4[:, :, 1], causal=True, out=att.view(B, S, nh, hd), k_len=ph["k_len"],
                               rope=(cos, sin, kn4, vn4) if fuse_rope else None)
-            self._linear(att, L, "o_w", w8, residual=src, out=x)
+            self._linear(att, L, "o_w", quant, residual=src, out=x)
             if fused_norm:
-                self._linear(x, L, "gu_w", w8, act="silu", glu=True, out=ff, prenorm=(L["n2"], 1e-6))
+                self._linear(x, L, "gu_w", quant, act="silu", glu=True, out=ff, prenorm=(L["n2"], 1e-6))
             else:
                 ops.norm(x, L["n2"], None, eps=1e-6, rms=True, out=h)
-                self._linear(h, L, "gu_w", w8, act="silu", glu=True, out=ff, w_frag=wf("gu_wf"))
-            self._linear(ff, L, "down_w", w8, residual=x, out=x, w_frag=wf("down_wf"))
+                self._linear(h, L, "gu_w", quant, act="silu", glu=True, out=ff, w_frag=wf("gu_wf"))
+            self._linear(ff, L, "down_w", quant, residual=x, out=x, w_frag=wf("down_wf"))
             if self.tap is not None:
                 self.tap("llm", li, x)
 
@@ -637,7 +700,7 @@ class QwenVLEngine:
             ops.norm(self.xl[:B], self.norm_w, None, eps=1e-6, rms=True, out=self.hl[:B], rows=B)
         else:
             ops.norm(self.x[: B * S], self.norm_w, None, eps=1e-6, rms=True, out=self.hl[:B], rows=B, in_map=(1, S, row_in_seq))
-        if self.w8_decode and B <= SKINNY_GEMM_MAX_ROWS:
+        if (self.w8_decode or self.mx4_decode) and B <= SKINNY_GEMM_MAX_ROWS:
             ops.linear_w8(self.hl[:B], *self.lm_head8, out=self.logits[:B])
         else:
             ops.linear(self.hl[:B], self.lm_head, out=self.logits[:B])     # (152064 columns: one wave per 16-column tile owns all of K)

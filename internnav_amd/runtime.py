@@ -102,6 +102,16 @@ def prof_read_w8() -> dict:
     return dict(ms=ms.value, launches=n.value, flops=fl.value, bytes=by.value)
 
 
+MX4_PROF = (4, 49)  # (class, sub) of the MXFP4-weight launches (ina_gemm_mx4) inside the weight-streaming class
+
+
+def prof_read_mx4() -> dict:
+    """the MXFP4-weight launches (ops.linear_mx4) of the weight-streaming class on their own; bytes count N * K / 2 + N * K / 32 per weight."""
+    ms, n, fl, by = C.c_double(), C.c_int64(), C.c_double(), C.c_double()
+    _lib.check(_lib.lib().ina_prof_read_sub(MX4_PROF[0], MX4_PROF[1], C.byref(ms), C.byref(n), C.byref(fl), C.byref(by)), "prof_read_sub")
+    return dict(ms=ms.value, launches=n.value, flops=fl.value, bytes=by.value)
+
+
 def prof_read() -> Dict[str, dict]:
     """Totals per kernel class since prof_enable(True): summed event-pair time (ms), launches, algorithmic FLOPs and bytes."""
     out = {}
