@@ -475,6 +475,33 @@ int ina_argmax_penalty_rows(const float* X, int32_t ldx, int32_t rows, int32_t n
 int ina_logprob_rows(const float* X, int32_t ldx, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
                      const int32_t* target, int32_t* tok, float* logprob, float* margin, void* stream);
 
+/* ---- sample_rows: one sampling step of HF generate(do_sample=True) - repetition penalty, temperature, top-k, top-p (HF's processor order) and
+ *      the draw - in ONE launch in place of the argmax / logprob launch. No random number is generated on the device: u holds one uniform
+ *      in [0, 1) per output row, drawn by the caller.
+ *  Output row r reads logits row s = src ? src[r] : r of X (f32 [x_rows, ldx], NOT modified); seen (uint32 [rows, ld_words], may be NULL), u
+ *  and every output are indexed by r, so K draws of one prompt can come from one logits row. A src entry outside [0, x_rows) is never
+ *  accessed: tok 0, logprob NaN, n_kept 0, thr NaN.
+ *   1. y = x, or the repetition-penalised row of argmax_penalty_rows over seen[r]; z = y / temperature, one IEEE fp32 division (bit-equal
+ *      to torch's scores / temperature). -0 counts as +0. NaN entries are never kept.
+ *   2. top_k > 0: with k = min(top_k, entries that are not NaN) and v_k the k-th largest z, keep z >= v_k (ties at v_k all stay, as
+ *      TopKLogitsWarper keeps them). 0 = off.
+ *   3. top_p < 1, over what top-k kept, with softmax masses p_i: a VALUE v stays iff the mass of the kept entries with z <= v is
+ *      > 1 - top_p. Entries that share a value stay or go together (tie-free rows: TopPLogitsWarper(min_tokens_to_keep=1); with ties the
+ *      superset of what HF keeps under any sort order); the maximum always stays. 1 = off (entries of mass 0 stay in the kept set).
+ *      thr[r] = the smallest kept value, n_kept[r] = the number of entries with z >= thr[r] (both may be NULL).
+ *   4. q_i = p_i / (kept mass); tok[r] = the first kept index, in ascending token id, whose inclusive cumulative q exceeds u[r].
+ *   5. logprob[r] = log q_tok: the log-softmax of HF's processed scores at the draw (compute_transition_scores(normalize_logits=True)),
+ *      with expf / logf.
+ *  -inf entries have mass 0 and are never drawn; a row with nothing above -inf gives tok 0, logprob NaN, n_kept 0, thr NaN. The result is
+ *  always in [0, n). mark != 0 (needs seen) sets the drawn token's bit in seen[r] in the same launch. Masses are summed as 44-bit fixed-point
+ *  integers: two launches on the same inputs give the same bits in every output. n <= 262144.
+ *  Refusals (X / tok / logprob / u NULL, rows < 0, x_rows < 1, n < 1, n > 262144, ldx < n, rows > x_rows without src, a temperature that is
+ *  not finite and > 0, top_k < 0, top_p outside (0, 1], ld_words * 32 < n or a penalty that is not finite and > 0 when seen is set, mark
+ *  without seen) return non-zero before any HIP call. Plain arguments: no struct, no ABI bump. */
+int ina_sample_rows(const float* X, int32_t ldx, int32_t x_rows, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
+                    float temperature, int32_t top_k, float top_p, const float* u, const int32_t* src, int32_t* tok, float* logprob, int32_t* n_kept,
+                    float* thr, void* stream);
+
 /* ---- select_traj: per env, rank the S samples by critic value; neg = the k lowest (ascending), pos = the k highest
  *      (descending); trajectories are cumsum_t(sample * scale).  reference: navdp_policy.py:317-320. */
 typedef struct ina_select_args {

@@ -230,6 +230,27 @@ int ina_logprob_rows(const float* X, int32_t ldx, int32_t rows, int32_t n, uint3
     return ina_launch_logprob(X, ldx, rows, n, seen, ld_words, penalty, mark, target, tok, logprob, margin, reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_sample_rows(const float* X, int32_t ldx, int32_t x_rows, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
+                    float temperature, int32_t top_k, float top_p, const float* u, const int32_t* src, int32_t* tok, float* logprob, int32_t* n_kept,
+                    float* thr, void* stream) {
+    INA_REQUIRE(X && tok && logprob && u, "sample_rows: X, tok, logprob and u required");
+    INA_REQUIRE(rows >= 0 && x_rows >= 1 && n >= 1 && ldx >= n, "sample_rows: bad arguments rows=%d x_rows=%d n=%d ldx=%d (rows >= 0, x_rows >= 1, n >= 1, ldx >= n)",
+                rows, x_rows, n, ldx);
+    INA_REQUIRE(src || rows <= x_rows, "sample_rows: rows=%d output rows of x_rows=%d logits rows need a src table", rows, x_rows);
+    INA_REQUIRE(n <= 262144, "sample_rows: a vocabulary of %d tokens exceeds 262144 (the fixed-point mass sum and the seen bitmap)", n);
+    INA_REQUIRE(std::isfinite(temperature) && temperature > 0.f, "sample_rows: temperature %g is not a strictly positive finite float", (double)temperature);
+    INA_REQUIRE(top_k >= 0, "sample_rows: top_k=%d is negative (0 switches top-k off)", top_k);
+    INA_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_rows: top_p=%g is outside (0, 1] (1 switches top-p off)", (double)top_p);
+    if (seen) {
+        INA_REQUIRE((long)ld_words * 32 >= (long)n, "sample_rows: ld_words=%d holds fewer than n=%d bits", ld_words, n);
+        INA_REQUIRE(std::isfinite(penalty) && penalty > 0.f, "sample_rows: repetition penalty %g is not a strictly positive finite float", (double)penalty);
+    }
+    INA_REQUIRE(!mark || seen, "sample_rows: mark needs a seen set");
+    if (rows == 0) return 0;
+    return ina_launch_sample(X, ldx, x_rows, rows, n, seen, ld_words, penalty, mark, temperature, top_k, top_p, u, src, tok, logprob, n_kept, thr,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_gemm_select(const ina_gemm_args* args, int* kernel) {
     INA_REQUIRE(args != nullptr && kernel != nullptr, "gemm_select: null argument");
     GemmArgs p;

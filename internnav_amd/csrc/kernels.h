@@ -81,6 +81,9 @@ int ina_launch_argmax_penalty(const float* X, int ldx, int rows, int n, uint32_t
                               hipStream_t stream);                                                                           // decode_penalty.hip
 int ina_launch_logprob(const float* X, int ldx, int rows, int n, uint32_t* seen, int ld_words, float penalty, int mark, const int32_t* target,
                        int32_t* tok, float* logprob, float* margin, hipStream_t stream);                                     // decode_logprob.hip
+int ina_launch_sample(const float* X, int ldx, int x_rows, int rows, int n, uint32_t* seen, int ld_words, float penalty, int mark, float temperature,
+                      int top_k, float top_p, const float* u, const int32_t* src, int32_t* tok, float* logprob, int32_t* n_kept, float* thr,
+                      hipStream_t stream);                                                                                   // decode_sample.hip
 int ina_launch_head3(const Head3Args& p, hipStream_t stream);
 int ina_launch_seqpool(const SeqpoolArgs& p, hipStream_t stream);
 int ina_launch_select(const SelectArgs& p, hipStream_t stream);

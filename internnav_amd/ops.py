@@ -768,6 +768,34 @@ def logprob_rows(x: torch.Tensor, tok: torch.Tensor, logprob: torch.Tensor, marg
     return logprob
 
 
+def sample_rows(x: torch.Tensor, u: torch.Tensor, tok: torch.Tensor, logprob: torch.Tensor, temperature: float = 1.0, top_k: int = 0,
+                top_p: float = 1.0, seen: Optional[torch.Tensor] = None, penalty: float = 1.0, mark: bool = False, src: Optional[torch.Tensor] = None,
+                n_kept: Optional[torch.Tensor] = None, thr: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One sampling step of HF generate(do_sample=True) per output row, in one launch: y = the f32 row of x (not modified) or, with `seen`, its
+    repetition-penalised row; z = y / temperature; top-k (0 = off, ties at the k-th value stay); top-p over what top-k kept (1 = off; a value
+    stays iff the softmax mass at or below it is > 1 - top_p, the maximum always); tok[r] = the first kept id whose inclusive cumulative
+    probability exceeds u[r] (f32 uniforms in [0, 1) drawn by the caller - nothing random happens on the device); logprob[r] = the log of
+    the drawn token's renormalised probability. src int32 [rows]: output row r reads x[src[r]] (K draws from one logits row; an entry
+    outside the rows of x gives tok 0 / logprob NaN); without it rows = x.shape[0]. mark sets the drawn bit in seen[r]. n_kept int32 /
+    thr f32 [rows] (optional): the size of the kept set and its smallest value. Deterministic: the same inputs give the same bits."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    x_rows, n = x.shape
+    rows = x_rows if src is None else src.numel()
+    assert tok.dtype == torch.int32 and tok.numel() == rows and tok.is_contiguous()
+    for t in (u, logprob, thr):
+        assert t is None or (t.dtype == torch.float32 and t.numel() == rows and t.is_contiguous())
+    assert n_kept is None or (n_kept.dtype == torch.int32 and n_kept.numel() == rows and n_kept.is_contiguous())
+    assert src is None or (src.dtype == torch.int32 and src.is_contiguous())
+    if seen is not None:
+        assert seen.dtype in (torch.uint32, torch.int32) and seen.dim() == 2 and seen.stride(1) == 1 and seen.shape[0] >= rows and seen.shape[1] * 32 >= n
+    p = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    rc = _lib.lib().ina_sample_rows(x.data_ptr(), x.stride(0), x_rows, rows, n, p(seen), seen.stride(0) if seen is not None else 0, float(penalty),
+                                    int(bool(mark)), float(temperature), int(top_k), float(top_p), u.data_ptr(), p(src), tok.data_ptr(),
+                                    logprob.data_ptr(), p(n_kept), p(thr), _stream())
+    _lib.check(rc, "sample_rows")
+    return tok
+
+
 def dit_v2t(kv2: torch.Tensor, heads: int, v2t: torch.Tensor) -> torch.Tensor:
     """condition V of a NextDiT block -> the transposed key-permuted image dit_attention consumes.
     kv2 bf16 [envs, Lz, 2, heads, 64] (K | V as produced by the fused kv projection); v2t bf16 [envs, heads, 64, 64]."""

@@ -200,7 +200,9 @@ def generation_config_from_hf(raw: Optional[dict], default_eos, ignore: bool = F
     """what `generate(do_sample=False)` honours of a checkpoint's generation_config.json (HF starts from that file and overrides only the
     keys it is passed): `repetition_penalty` (default 1.0) and `eos_token_id` (an int or a list; default: config.json's) -> a namespace with
     repetition_penalty, eos_token_id (tuple) and the raw dict. raw None = no file: penalty 1.0, EOS of config.json.
-    Sampling-only keys (do_sample, temperature, top_k, top_p, min_p, typical_p) are ignored, as HF ignores them under do_sample=False.
+    Sampling-only keys (do_sample, temperature, top_k, top_p, min_p, typical_p) are ignored by greedy decoding, as HF ignores them under
+    do_sample=False; the namespace carries the file's do_sample / temperature / top_k / top_p (None = not set) for generate(do_sample=True)
+    (`sampling_spec`, which is also where min_p / typical_p / epsilon_cutoff / eta_cutoff are refused - at generate() time, not here).
     A key that changes greedy output and is not implemented raises NotImplementedError naming it, unless `ignore`."""
     raw = dict(raw or {})
     bad = sorted(k for k, ok in _GEN_REFUSED.items() if k in raw and not ok(raw[k]))
@@ -213,7 +215,46 @@ def generation_config_from_hf(raw: Optional[dict], default_eos, ignore: bool = F
     if not (np.isfinite(pen) and pen > 0.0):
         raise ValueError(f"generation_config.json: repetition_penalty={raw.get('repetition_penalty')!r} is not a strictly positive float")
     eos = raw.get("eos_token_id")
-    return SimpleNamespace(repetition_penalty=pen, eos_token_id=eos_ids(default_eos if eos is None else eos), raw=raw)
+    # the file's sampling keys as they stand (None = not in the file): read only by generate(do_sample=True) (`sampling_spec`), never by greedy
+    return SimpleNamespace(repetition_penalty=pen, eos_token_id=eos_ids(default_eos if eos is None else eos), raw=raw,
+                           do_sample=raw.get("do_sample"), temperature=raw.get("temperature"), top_k=raw.get("top_k"), top_p=raw.get("top_p"))
+
+
+# sampling keys that are not implemented: key -> is this value HF's "off"?
+_SAMPLING_REFUSED = {"min_p": lambda v: v is None, "typical_p": lambda v: v is None or float(v) == 1.0,
+                     "epsilon_cutoff": lambda v: v is None or float(v) == 0.0, "eta_cutoff": lambda v: v is None or float(v) == 0.0}
+
+
+def sampling_spec(gen_cfg: SimpleNamespace, do_sample: bool, temperature=None, top_k=None, top_p=None, num_return_sequences: Optional[int] = None,
+                  extra: Optional[dict] = None) -> Optional[SimpleNamespace]:
+    """what generate() samples with, resolved as HF resolves it (host only): None under do_sample=False (the file's sampling keys and the
+    sampling kwargs are ignored, as HF ignores them), else a namespace temperature / top_k (0 = off) / top_p / K = num_return_sequences.
+    A None argument takes generation_config.json's value; without one HF's defaults apply: temperature 1.0, top_k 50, top_p 1.0.
+    ValueError (as HF): num_return_sequences > 1 without do_sample; a temperature that is not a strictly positive finite float; top_k < 0;
+    top_p outside (0, 1]. NotImplementedError naming the key: min_p, typical_p, epsilon_cutoff or eta_cutoff set to something other than
+    off, in the kwargs (`extra`) or the file - at generate() time, never at load."""
+    K = 1 if num_return_sequences is None else int(num_return_sequences)
+    if K < 1:
+        raise ValueError(f"num_return_sequences={num_return_sequences!r} must be >= 1")
+    if not do_sample:
+        if K > 1:
+            raise ValueError(f"num_return_sequences={K} > 1 needs do_sample=True: greedy decoding returns one sequence per prompt (as HF)")
+        return None
+    extra = extra or {}
+    for k, off in _SAMPLING_REFUSED.items():
+        v = extra[k] if extra.get(k) is not None else gen_cfg.raw.get(k)
+        if not off(v):
+            raise NotImplementedError(f"generate(do_sample=True): {k}={v!r} is set ({'argument' if extra.get(k) is not None else 'generation_config.json'}) "
+                                      "and is not implemented; sampling without it would draw from another distribution than transformers does")
+    pick = lambda arg, name, default: arg if arg is not None else (default if getattr(gen_cfg, name, None) is None else getattr(gen_cfg, name))      # noqa: E731
+    T, tk, tp = float(pick(temperature, "temperature", 1.0)), int(pick(top_k, "top_k", 50) or 0), float(pick(top_p, "top_p", 1.0))
+    if not (np.isfinite(T) and T > 0.0):
+        raise ValueError(f"do_sample=True: temperature={T!r} has to be a strictly positive float (use do_sample=False for greedy decoding)")
+    if tk < 0:
+        raise ValueError(f"do_sample=True: top_k={tk!r} has to be >= 0 (0 = off)")
+    if not 0.0 < tp <= 1.0:
+        raise ValueError(f"do_sample=True: top_p={tp!r} has to be in (0, 1] (1 = off)")
+    return SimpleNamespace(temperature=T, top_k=tk, top_p=tp, K=K)
 
 
 SCORE_SLAB_ROWS = 256      # rows of the fp32 [rows, vocab] logit buffer of score_answers (156 MB at 152064 tokens), allocated on first use
@@ -350,6 +391,7 @@ class InternVLAN1ForCausalLM:
         else:
             self.s1 = NavDPPolicyDAT(_Prefixed(weights, "model.navdp."), s1_cfg or synthetic.N1_NAVDP_CFG, device, max_envs, use_async="async" in system1)
         self._noise_gen = torch.Generator(device=self.device).manual_seed(0)
+        self._sample_gen = torch.Generator(device="cpu").manual_seed(0)      # default source of generate(do_sample=True)'s uniforms: advances per call
         self.kv_reuse_rows = 0          # prompt rows generate(past_key_values=...) took from caches instead of prefilling them (cumulative)
         self.kv_reuse_fallbacks = 0     # rows that had to run without their cache: the run rectangle would not fit the engine (cumulative)
         self.last_kv_reuse = dict(rows=0, fallbacks=0)
@@ -407,8 +449,10 @@ class InternVLAN1ForCausalLM:
     def generate(self, input_ids=None, pixel_values=None, image_grid_thw=None, attention_mask=None, max_new_tokens: int = 128,
                  do_sample: bool = False, use_cache: bool = True, past_key_values=None, return_dict_in_generate: bool = False,
                  decode_chunk: int = 8, eos_token_id=None, cached_image_embeds: Optional[list] = None, prefix_kv: Optional[list] = None,
-                 export_prefix: Optional[list] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False, **_):
-        """greedy decoding (do_sample=False is the only mode the reference uses, internvla_n1_policy.py:169-176). Decodes in chunks of
+                 export_prefix: Optional[list] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
+                 temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                 num_return_sequences: Optional[int] = None, generator: Optional[torch.Generator] = None, seed: Optional[int] = None, **kw):
+        """greedy decoding by default (do_sample=False is the only mode the reference uses, internvla_n1_policy.py:169-176). Decodes in chunks of
         `decode_chunk` device-side steps and stops once every sequence has emitted EOS. Sequences are right-filled with EOS.
         repetition_penalty / eos_token_id: None = the checkpoint's generation_config.json (`self.generation_config`; without that file 1.0
         and config.json's EOS), an explicit value overrides it as HF kwargs do. The penalty acts on every greedy step over prompt + answer
@@ -431,9 +475,30 @@ class InternVLAN1ForCausalLM:
         `.token_logprobs` f32 [B, n] - per answer token the log-softmax of the PROCESSED scores (after the repetition penalty) at that token,
         what HF's compute_transition_scores(sequences, scores, normalize_logits=True) returns -, `.token_margins` [B, n] (distance of the
         chosen logit to the runner-up), `.sequences_logprob` [B] (the sum up to and including EOS) and `.answer_lengths` int64 [B] (tokens of
-        each answer up to and including its first EOS: the positions the sum runs over); positions behind a row's first EOS hold 0.0. output_scores / output_logits stay swallowed: no [B, vocab] tensor is returned."""
-        assert not do_sample, "the reference only decodes greedily"
-        if output_logprobs and not self.qwen.token_logprobs:
+        each answer up to and including its first EOS: the positions the sum runs over); positions behind a row's first EOS hold 0.0. output_scores / output_logits stay swallowed: no [B, vocab] tensor is returned.
+        do_sample=True (opt-in; greedy launches what it always launched): HF's multinomial sampling - repetition penalty, temperature, top-k,
+        top-p in HF's processor order, then the draw - in one device launch per step in place of the argmax (ops.sample_rows).
+        temperature / top_k / top_p: None = generation_config.json's value, without the file HF's defaults 1.0 / 50 / 1.0 (`sampling_spec`,
+        which also names the refusals). The uniforms come from `generator` (a CPU torch.Generator), else from a fresh generator seeded
+        `seed`, else from the model's own CPU generator (seeded 0 at construction, advancing per call): the same seed gives the same
+        sequences. num_return_sequences=K: every prompt is prefilled ONCE (its images encoded once), its K first tokens are drawn from the
+        one logits row and its cache rows are replicated into K slots; `sequences` is [B * K, S + n], prompt-major like HF's
+        repeat_interleave; B * K beyond the engine's max_seqs raises CapacityError before anything is launched. With K > 1 the result
+        carries past_key_values=None, export_prefix is refused (ValueError), and generate_latents on a returned row takes the
+        reference-signature re-run path (the cached state is of B * K rows). output_logprobs under sampling works on every model
+        (token_logprobs=True is not needed: the sampling path keeps its own buffer): token_logprobs = log q of each draw, the log-softmax
+        of HF's processed scores (after penalty, temperature, top-k, top-p); token_margins is not defined for a draw and is NaN inside
+        the answer (0.0 behind EOS, like every masked position); answer_confidences' margin of a sampled row is NaN accordingly."""
+        smp = sampling_spec(self.generation_config, do_sample, temperature, top_k, top_p, num_return_sequences, kw)
+        if smp is not None:
+            if smp.K > 1 and export_prefix is not None and any(export_prefix):
+                raise ValueError("export_prefix is not supported with num_return_sequences > 1: export the prefix from a call with one sequence per prompt")
+            if input_ids.shape[0] * smp.K > self.qwen.B_max:
+                raise CapacityError(f"{input_ids.shape[0]} prompts x num_return_sequences={smp.K} exceed the engine's max_seqs={self.qwen.B_max}")
+            if max_new_tokens > self.qwen.max_decode:
+                raise CapacityError(f"max_new_tokens={max_new_tokens} exceeds the max_decode={self.qwen.max_decode} log-probability columns of the "
+                                    "sampling path: build the model with a larger max_decode (from_pretrained(..., max_decode=N))")
+        if output_logprobs and smp is None and not self.qwen.token_logprobs:
             raise ValueError("generate(output_logprobs=True) needs the engine setting token_logprobs: build the model with "
                              "token_logprobs=True (from_pretrained(..., token_logprobs=True) / model_settings['token_logprobs'] = True)")
         if self.qwen.token_logprobs and max_new_tokens > self.qwen.max_decode:
@@ -474,7 +539,7 @@ class InternVLAN1ForCausalLM:
                 keep = [pv[off[i]:off[i + 1]] for i, s in enumerate(skip) if not s]
                 pv = torch.cat(keep, 0) if keep else None
         state = self.qwen.prefill(input_ids, pv, image_grid_thw, cached_embeds=cached_image_embeds, seq_lens=plens if attention_mask is not None else None,
-                                  prefix_len=pl, **({} if penalty == 1.0 else {"repetition_penalty": penalty}))
+                                  prefix_len=pl, **({} if penalty == 1.0 else {"repetition_penalty": penalty}), **self._sampling_kw(smp, B, max_new_tokens, generator, seed))
         self._prefix_out = {}
         if export_prefix is not None:
             for b, n in enumerate(export_prefix):
@@ -497,11 +562,15 @@ class InternVLAN1ForCausalLM:
             e = int(hit[0]) + 1 if hit.numel() else toks.shape[1]
             toks[b, e:] = eos
             lens.append(e)
-        self._gen = dict(state=state, tokens=toks, lens=np.asarray(lens), prompt_lens=plens)
-        # every row = its own prompt, then its answer, right-filled with EOS to the common width S + n
+        K = 1 if smp is None else smp.K
         ids_cpu = input_ids.cpu().long()
-        seqs = torch.full((B, S + toks.shape[1]), eos, dtype=torch.long)
-        for b in range(B):
+        if K > 1:                                                 # rows are prompt-major from here on: row b * K + c = prompt b, sequence c
+            plens, ids_cpu = np.repeat(plens, K), ids_cpu.repeat_interleave(K, dim=0)
+        # (K > 1: the cached state is of B * K rows and a caller continues ONE returned row: generate_latents re-runs it, the reference signature)
+        self._gen = dict(state=state, tokens=toks, lens=np.asarray(lens), prompt_lens=plens) if K == 1 else None
+        # every row = its own prompt, then its answer, right-filled with EOS to the common width S + n
+        seqs = torch.full((B * K, S + toks.shape[1]), eos, dtype=torch.long)
+        for b in range(B * K):
             L = int(plens[b])
             seqs[b, :L] = ids_cpu[b, :L]
             seqs[b, L:L + toks.shape[1]] = toks[b]
@@ -509,7 +578,11 @@ class InternVLAN1ForCausalLM:
         if not return_dict_in_generate:
             return seqs
         lp_out = {}
-        if output_logprobs:
+        if output_logprobs and smp is not None:
+            lp = self.qwen.last_sample_logprobs(state)         # one column per draw
+            assert lp.shape == toks.shape, (lp.shape, toks.shape)
+            lp_out = vars(answer_logprob_summary(lp, torch.full_like(lp, float("nan")), lens))
+        elif output_logprobs:
             lp, mg = self.qwen.last_logprobs(state)            # one column per selection = per emitted token, chunked or not
             assert lp.shape[1] == toks.shape[1], (lp.shape, toks.shape)
             lp_out = vars(answer_logprob_summary(lp, mg, lens))
@@ -517,8 +590,19 @@ class InternVLAN1ForCausalLM:
         # a real prompt: only the rows it took from a cache are exact
         exact = int(state["S_run"]) >= ATTN_WIDE_MIN_ROWS and B * int(state["S_run"]) > SKINNY_GEMM_MAX_ROWS
         keep = plens if exact else np.broadcast_to(np.asarray(pl, dtype=np.int64), (B,))
-        pkv = self.qwen.kv_handle([ids_cpu[b, : int(keep[b])] for b in range(B)]) if use_cache else None
+        pkv = self.qwen.kv_handle([ids_cpu[b, : int(keep[b])] for b in range(B)]) if use_cache and K == 1 else None
         return SimpleNamespace(sequences=seqs, past_key_values=pkv, **lp_out)
+
+    def _sampling_kw(self, smp, B: int, max_new_tokens: int, generator, seed) -> dict:
+        """the engine's sampling spec of one generate() call ({} = greedy): the uniforms of every step and returned sequence, drawn HERE on
+        the host (one f32 [max_new_tokens, B * K] table, one copy to the device) - no random number is generated in a kernel"""
+        if smp is None:
+            return {}
+        if generator is not None:
+            assert isinstance(generator, torch.Generator) and generator.device.type == "cpu", "generator: a CPU torch.Generator"
+        gen = generator if generator is not None else (torch.Generator(device="cpu").manual_seed(int(seed)) if seed is not None else self._sample_gen)
+        u = torch.rand(max_new_tokens, B * smp.K, generator=gen, dtype=torch.float32).to(self.device)
+        return {"sampling": dict(temperature=smp.temperature, top_k=smp.top_k, top_p=smp.top_p, u=u, K=smp.K)}
 
     def score_answers(self, input_ids, answers, pixel_values=None, image_grid_thw=None, attention_mask=None, share_prefix: bool = False,
                       max_suffix_rows: Optional[int] = None) -> SimpleNamespace:

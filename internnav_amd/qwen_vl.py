@@ -407,6 +407,7 @@ class QwenVLEngine:
         # launch writes is one contiguous row at an address fixed per step (capturable); tok_logprob / tok_margin are the [B_max, max_decode] views
         self.token_logprobs, self.max_decode = bool(token_logprobs), int(max_decode)
         self._lp_steps = self._mg_steps = self.tok_logprob = self.tok_margin = None      # (no buffer at all without the setting)
+        self._smp_lp = None      # sampling (prefill(sampling=)): log-probability of the draws, step-major f32 [max_decode, max_seqs], allocated by the first sampling call
         if self.token_logprobs:
             self._lp_steps, self._mg_steps = (torch.zeros(self.max_decode, max_seqs, dtype=f32, device=dev) for _ in range(2))
             self.tok_logprob, self.tok_margin = self._lp_steps.t(), self._mg_steps.t()
@@ -690,11 +691,15 @@ class QwenVLEngine:
         self._layers(ph)
         return self.x[: P * m]
 
-    def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None, penalty: Optional[float] = None, col: int = 0):
+    def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None, penalty: Optional[float] = None, col: int = 0,
+                     sampling: Optional[dict] = None, src: Optional[torch.Tensor] = None):
         """final RMSNorm + lm_head on ONE row per sequence, greedy argmax on the device. row_in_seq: the same row for every sequence,
         or (ragged batches) rows_idx int32 [B] = absolute row of each sequence's last real token. penalty: the selection runs over the
         repetition-penalised logits of the tokens in `seen` and marks the chosen one (`logits` keeps the raw values).
-        col (token_logprobs engines): the answer position this selection produces = the column of tok_logprob / tok_margin it fills."""
+        col (token_logprobs engines): the answer position this selection produces = the column of tok_logprob / tok_margin it fills.
+        sampling (state["sampling"]): ops.sample_rows IN PLACE of the argmax / logprob launch - temperature, top-k, top-p and the draw against
+        row `col` of the state's uniform table; the draw's log-probability goes to column col of the sampling buffer. src int32 [B * K]: the
+        output rows (one per returned sequence, with its own seen set) read the B logits rows through it."""
         if rows_idx is not None:
             ops.gather_rows(self.x[: B * S], self.xl[:B], src=rows_idx)
             ops.norm(self.xl[:B], self.norm_w, None, eps=1e-6, rms=True, out=self.hl[:B], rows=B)
@@ -704,7 +709,13 @@ class QwenVLEngine:
             ops.linear_w8(self.hl[:B], *self.lm_head8, out=self.logits[:B])
         else:
             ops.linear(self.hl[:B], self.lm_head, out=self.logits[:B])     # (152064 columns: one wave per 16-column tile owns all of K)
-        if self.token_logprobs:
+        if sampling is not None:
+            R = B if src is None else src.numel()
+            assert col < sampling["u"].shape[0] and col < self._smp_lp.shape[0] and R <= sampling["u"].shape[1], (col, R, sampling["u"].shape)
+            ops.sample_rows(self.logits[:B], sampling["u"][col, :R], self.next_tok[:R], self._smp_lp[col, :R], temperature=sampling["temperature"],
+                            top_k=sampling["top_k"], top_p=sampling["top_p"], seen=None if penalty is None else self.seen,
+                            penalty=1.0 if penalty is None else penalty, mark=penalty is not None, src=src)
+        elif self.token_logprobs:
             # the same selection (bit-equal ids) + log-softmax at the chosen index and the top-2 margin, in the launch that replaces the argmax
             assert col < self.max_decode, (col, self.max_decode)     # (plan() / decode() refuse longer answers before anything is launched)
             ops.logprob_rows(self.logits[:B], self.next_tok[:B], self._lp_steps[col, :B], self._mg_steps[col, :B],
@@ -724,6 +735,30 @@ class QwenVLEngine:
                                "model_settings['token_logprobs'] / from_pretrained(token_logprobs=True))")
         n = int(state["n_sel"]) if "n_sel" in state else int(state.get("n_decode", 0))
         return self.tok_logprob[: state["B"], :n], self.tok_margin[: state["B"], :n]
+
+    def last_sample_logprobs(self, state: dict) -> torch.Tensor:
+        """f32 [rows, n] device view: log q of every token drawn so far from a sampling `state` (rows = B * num_return_sequences), the
+        log-softmax of HF's processed scores (penalty, temperature, top-k, top-p) at the draw. A view: the next sampling call overwrites it."""
+        assert "sampling" in state, "not a sampling state (prefill(..., sampling=...))"
+        return self._smp_lp.t()[: state["B"], : int(state.get("n_sel", 0))]
+
+    def _fan_out(self, state: dict, K: int):
+        """num_return_sequences = K behind ONE prefill: the prompt rows of cache slot b go to slots b * K + c (ina_kv_copy, out to temporary
+        tensors and back in - source slots are destinations too: two launches for the whole batch), and `state` becomes the decode state of
+        B * K rows (prompt-major, HF's repeat_interleave): next_pos / lens / cur replicated. The seen rows were replicated in front of the
+        first draw, which marks them per returned sequence."""
+        B, lens = state["B"], state.get("lens")
+        n = np.full(B, state["S"], dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64)
+        self._kv_evict({slot: 0 for slot in range(B * K)})
+        tmp = [torch.empty(len(self.layers), int(n[b]), self.kv_w, dtype=torch.bfloat16, device=self.device) for b in range(B)]
+        self._kv_copy([(tmp[b], b, int(n[b])) for b in range(B)], to_engine=False)
+        self._kv_copy([(tmp[b], b * K + c, int(n[b])) for b in range(B) for c in range(K)], to_engine=True)
+        state["B"] = B * K
+        state["next_pos"] = np.repeat(np.asarray(state["next_pos"]), K)
+        if lens is not None:
+            state["lens"] = np.repeat(n, K)
+            state["cur"] = state["lens"].copy()
+        state["fan"] = K
 
     def _seen_init(self, P: dict):
         """launch in front of a decode's first selection: every sequence's seen set = its whole prompt (cached prefix included)"""
@@ -1073,15 +1108,44 @@ class QwenVLEngine:
 
     # ---- eager, stateful API (used by the policy layer: answers have data-dependent lengths)
     def prefill(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor], image_grid_thw, cached_embeds: Optional[list] = None,
-                seq_lens=None, prefix_len: int = 0, repetition_penalty: float = 1.0) -> dict:
+                seq_lens=None, prefix_len: int = 0, repetition_penalty: float = 1.0, sampling: Optional[dict] = None) -> dict:
         """seq_lens [B] (optional): RAGGED batch - input_ids is right-padded to a common length S and sequence b has seq_lens[b] real
         tokens. Causal attention keeps every real position independent of the padding behind it, so the prefill runs on the padded
         rectangle; the first token is read at each sequence's own last position and the decode / latent passes append at per-sequence
-        cache positions with per-sequence key lengths (the pad rows' K/V are never attended and get overwritten)."""
+        cache positions with per-sequence key lengths (the pad rows' K/V are never attended and get overwritten).
+        sampling (opt-in; None = greedy, the launch sequence it always was): dict(temperature > 0, top_k >= 0 (0 = off), top_p in (0, 1],
+        u = f32 [steps, B * K] uniforms in [0, 1) drawn by the caller (row j serves answer token j), K = num_return_sequences, default 1).
+        `decode` then draws every token with ops.sample_rows in place of the argmax launch (HF do_sample=True: penalty, temperature, top-k,
+        top-p, multinomial) and keeps the draws' log-probabilities in a buffer of its own, allocated here on the first sampling call - an
+        engine without token_logprobs=True samples as well (`last_sample_logprobs`). K > 1: the B prompts are prefilled once (images encoded
+        once), the K first tokens of prompt b are drawn from its ONE logits row, its cache rows are replicated into slots b * K + c
+        (`_fan_out`) and decoding continues with B * K rows, prompt-major; B * K > max_seqs raises CapacityError before anything is launched.
+        plan() / run_decode (the graph path) stay greedy."""
+        if sampling is not None:
+            sampling = self._sampling_state(sampling, input_ids.shape[0])
         P = self.plan(input_ids, image_grid_thw, cached_embeds=cached_embeds, prefix_len=prefix_len, repetition_penalty=repetition_penalty,
                       seq_lens=seq_lens)
         self.run_prefill(P, pixel_values)
-        return self.prefill_state(P, input_ids, image_grid_thw, seq_lens)
+        st = self.prefill_state(P, input_ids, image_grid_thw, seq_lens)
+        if sampling is not None:
+            st["sampling"] = sampling
+        return st
+
+    def _sampling_state(self, spec: dict, B: int) -> dict:
+        """validated copy of a sampling spec (`prefill`); allocates the sampling log-probability buffer on the first call"""
+        K = int(spec.get("K", 1))
+        T, top_k, top_p, u = float(spec["temperature"]), int(spec.get("top_k", 0) or 0), float(spec.get("top_p", 1.0)), spec["u"]
+        if K < 1 or not (np.isfinite(T) and T > 0.0) or top_k < 0 or not 0.0 < top_p <= 1.0:
+            raise ValueError(f"sampling spec: temperature={T} (> 0), top_k={top_k} (>= 0), top_p={top_p} (in (0, 1]), K={K} (>= 1)")
+        if B * K > self.B_max:
+            raise CapacityError(f"{B} prompts x {K} returned sequences exceed the engine's max_seqs={self.B_max}")
+        if not (u.dtype == torch.float32 and u.dim() == 2 and u.shape[1] == B * K and u.is_contiguous() and u.device == self.device):
+            raise ValueError(f"sampling spec: u must be a contiguous f32 [steps, {B * K}] tensor on {self.device}")
+        if u.shape[0] > self.max_decode:
+            raise CapacityError(f"{u.shape[0]} sampling steps exceed the engine's max_decode={self.max_decode} log-probability columns")
+        if self._smp_lp is None:
+            self._smp_lp = torch.zeros(self.max_decode, self.B_max, dtype=torch.float32, device=self.device)
+        return dict(temperature=T, top_k=top_k, top_p=top_p, u=u, K=K)
 
     def prefill_state(self, P: dict, input_ids, image_grid_thw, seq_lens=None) -> dict:
         """the host-side state `prefill` returns for a plan that has been run (decode / latent passes continue from it): a function of the
@@ -1105,27 +1169,40 @@ class QwenVLEngine:
         returned token is sampled but not yet run through the layers (its K/V are not cached)."""
         B, S = state["B"], state["S"]
         Sr = state.get("S_run", S)                                # rows per sequence in x (prompt minus a cached prefix)
-        out = torch.empty(B, n_steps, dtype=torch.int32, device=self.device)
+        smp = state.get("sampling")                               # None: greedy
+        K = smp["K"] if smp is not None and "cur" not in state else 1      # > 1: this call makes the first draw and fans the batch out
+        out = torch.empty(B * K, n_steps, dtype=torch.int32, device=self.device)
         lens = state.get("lens")
         pen = state["plan"].get("rep_penalty")
+        if smp is not None and state.get("n_sel", 1) + n_steps - 1 > smp["u"].shape[0]:          # before anything is launched
+            raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} exceeds the {smp['u'].shape[0]} rows of the sampling state's uniform table")
         if self.token_logprobs and state.get("n_sel", 1) + n_steps - 1 > self.max_decode:      # before anything is launched
             raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} exceeds the engine's max_decode={self.max_decode} "
                                 "log-probability columns")
         if "cur" not in state:
             if pen is not None:
                 self._seen_init(state["plan"])
+            kw = {} if smp is None else {"sampling": smp}
+            if K > 1:
+                kw["src"] = torch.arange(B, dtype=torch.int32, device=self.device).repeat_interleave(K)
+                if pen is not None:                               # one seen set per returned sequence: the draw marks row b * K + c
+                    bits = self.seen.view(torch.int32)
+                    bits[: B * K].copy_(bits[:B].repeat_interleave(K, dim=0))
             if lens is None and bool((state["plan"]["prefix_len"] == state["plan"]["prefix_len"][0]).all()):
-                self._last_logits(B, Sr, Sr - 1, penalty=pen, col=0)
+                self._last_logits(B, Sr, Sr - 1, penalty=pen, col=0, **kw)
                 state["cur"] = S
             elif lens is None:       # equal-length prompts behind prefixes of different lengths: each sequence's last real row
                 rows = torch.from_numpy((np.arange(B) * Sr + S - state["plan"]["prefix_len"] - 1).astype(np.int32)).to(self.device)
-                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen, col=0)
+                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen, col=0, **kw)
                 state["cur"] = S
             else:
                 rows = torch.from_numpy((np.arange(B) * Sr + lens - state["plan"]["prefix_len"] - 1).astype(np.int32)).to(self.device)
-                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen, col=0)
+                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen, col=0, **kw)
                 state["cur"] = lens.copy()
             state["n_sel"] = 1                                    # selections made so far = answer tokens with a log-probability column
+            if K > 1:
+                self._fan_out(state, K)
+                B, lens = state["B"], state.get("lens")
         for j in range(n_steps):
             out[:, j].copy_(self.next_tok[:B])
             if j == n_steps - 1:
@@ -1136,7 +1213,7 @@ class QwenVLEngine:
                 self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur))
             else:
                 self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur, k_len=cur + 1))
-            self._last_logits(B, 1, 0, penalty=pen, col=state["n_sel"])
+            self._last_logits(B, 1, 0, penalty=pen, col=state["n_sel"], **({} if smp is None else {"sampling": smp}))
             state["n_sel"] += 1
             state["cur"] = cur + 1
             state["next_pos"] = state["next_pos"] + 1
