@@ -179,7 +179,10 @@ typedef struct ina_attn_args {
      * and their KV-cache append inside the attention launch - what ina_rope_bf16 with KV set does in a launch of its own. Q holds the UN-rotated
      * query heads; k_new / v_new the un-rotated key / raw value heads of the Lq new tokens (element strides kn_bs per sequence, kn_rs per token,
      * kn_hs per kv head - the q|k|v projection buffer); the kernel rotates q in registers, writes rotate(k_new) and v_new into rows
-     * len_k - Lq .. len_k - 1 of K / V (the cache) and then attends. Same arithmetic and rounding as the separate launch. NULL: Q / K / V as given. */
+     * len_k - Lq .. len_k - 1 of K / V (the cache) and then attends. Same arithmetic and rounding as the separate launch. NULL: Q / K / V as given.
+     * PRECONDITION (the caller's: k_len lives on the device, the host-side checks cannot see it): every k_len[b] >= Lq (and Lk >= Lq without
+     * k_len) - len_k counts the new tokens; a smaller k_len[b] would put the append rows BEFORE row 0 of the cache, and the kernel does not guard
+     * that write. Without rope_cos any k_len[b] >= 0 is fine (rows without a key come out as zeros). */
     const float* rope_cos;     /* f32 [B * Lq, 128] or NULL */
     const float* rope_sin;
     const void* k_new;
