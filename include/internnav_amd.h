@@ -307,6 +307,30 @@ int ina_attention_prefix(const void* Q, int64_t q_ps, int64_t q_rs, int64_t q_hs
                          const void* v_suf, int64_t s_ps, int64_t s_rs, int64_t s_hs, const int32_t* slot, const int32_t* pfx_len,
                          const int32_t* suf_len, int32_t P, int32_t m, int32_t H, int32_t Hkv, int32_t D, int32_t max_pfx, float scale, void* stream);
 
+/* ---- attention_shared: single-token attention of n_rows rows (one returned sequence each) whose prompts stay ONCE in the System-2 KV cache,
+ *      one launch (generate(do_sample=True, num_return_sequences=K, share_prefix=True): K sampled answers per prompt, no cache slot per answer).
+ *  bf16 in / out, fp32 softmax and accumulation, strides in elements, D = 128, G = H / Hkv <= 16.
+ *  Q, O       n_rows rows x H heads x D: element (r, h, d) at r * ?_rs + h * ?_hs + d;
+ *  k_cache, v_cache   the engine's cache layout: key / value row i of slot s, KV head kh at s * c_ss + i * c_rs + kh * c_hs (one set of
+ *             strides for both pointers), n_slots slots, at least max_pfx rows in each;
+ *  k_tail, v_tail     the rows' own keys / values (their answer tokens, the current one included), in the cache's row format: tail row t of
+ *             row r, KV head kh at r * t_ps + t * t_rs + kh * t_hs (one set of strides for both pointers), T tail rows per row;
+ *  tile_rows  device int32 [n_tiles, cpt], cpt = 16 / G: the rows that share one 16-row MFMA tile - rows of the SAME prompt -, -1 = an empty
+ *             place (skipped; so is an index outside [0, n_rows)); a row named twice is computed twice;
+ *  tile_slot, tile_pfx   device int32 [n_tiles]: the cache slot of the tile's prompt and its cached length; tail_len device int32 [n_rows].
+ *  Row r of tile t sees keys 0 .. min(tile_pfx[t], max_pfx) - 1 of cache slot tile_slot[t] and the first min(tail_len[r], T) rows of its own
+ *  tail: nothing of another row's tail, no cache row at or behind tile_pfx[t]. tail_len[r] <= 0: the row comes out as zeros. A tile_slot[t]
+ *  outside [0, n_slots) yields NaN in the rows of that tile that have a tail (zeros in the others) and never an out-of-bounds access. Rows no
+ *  tile names are not written. Nothing is written to the cache. The bits of a row do not depend on which rows share its tile nor on their
+ *  tail lengths; no atomics, no workspace: two launches give the same bits; device tables only: graph capturable.
+ *  Contract: D = 128, H % Hkv = 0, H / Hkv <= 16, n_tiles / n_rows / T >= 1, max_pfx >= 0, n_slots >= 1, 16-byte aligned Q / K / V rows (strides
+ *  multiples of 8, pointers of 16 bytes), 8-byte aligned O rows; anything else is refused before any HIP call.
+ *  Plain arguments: no struct, no ABI bump. */
+int ina_attention_shared(const void* Q, int64_t q_rs, int64_t q_hs, void* O, int64_t o_rs, int64_t o_hs, const void* k_cache, const void* v_cache,
+                         int64_t c_ss, int64_t c_rs, int64_t c_hs, int32_t n_slots, const void* k_tail, const void* v_tail, int64_t t_ps, int64_t t_rs,
+                         int64_t t_hs, int32_t T, const int32_t* tile_rows, const int32_t* tile_slot, const int32_t* tile_pfx, const int32_t* tail_len,
+                         int32_t n_tiles, int32_t n_rows, int32_t H, int32_t Hkv, int32_t D, int32_t max_pfx, float scale, void* stream);
+
 /* ---- memory_gather: the visual-memory rows of the NavDPNet former's token buffer for n stepped envs of a rollout, from a per-env ring of
  *      cached frame tokens, in ONE launch (graph capturable; reference memory semantics: navdp_lerobot_dataset.py:215-222).
  *  ring  f32 [max_envs, depth, ntok, C]: final-LayerNorm tokens of each env's last depth = (M - 1) * stride + 1 frames, without positions;

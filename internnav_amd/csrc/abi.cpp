@@ -196,6 +196,15 @@ int ina_attention_prefix(const void* Q, int64_t q_ps, int64_t q_rs, int64_t q_hs
                                        H, Hkv, D, max_pfx, scale, reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_attention_shared(const void* Q, int64_t q_rs, int64_t q_hs, void* O, int64_t o_rs, int64_t o_hs, const void* k_cache, const void* v_cache,
+                         int64_t c_ss, int64_t c_rs, int64_t c_hs, int32_t n_slots, const void* k_tail, const void* v_tail, int64_t t_ps, int64_t t_rs,
+                         int64_t t_hs, int32_t T, const int32_t* tile_rows, const int32_t* tile_slot, const int32_t* tile_pfx, const int32_t* tail_len,
+                         int32_t n_tiles, int32_t n_rows, int32_t H, int32_t Hkv, int32_t D, int32_t max_pfx, float scale, void* stream) {
+    return ina_launch_attention_shared(Q, (long)q_rs, (long)q_hs, O, (long)o_rs, (long)o_hs, k_cache, v_cache, (long)c_ss, (long)c_rs, (long)c_hs,
+                                       n_slots, k_tail, v_tail, (long)t_ps, (long)t_rs, (long)t_hs, T, tile_rows, tile_slot, tile_pfx, tail_len,
+                                       n_tiles, n_rows, H, Hkv, D, max_pfx, scale, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_memory_gather(void* out, int64_t out_env_stride, float* ring, const float* fresh, const float* blank, const float* pe, const int32_t* env,
                       const int32_t* head, const int32_t* count, int32_t n, int32_t max_envs, int32_t M, int32_t ntok, int32_t C, int32_t depth,
                       int32_t stride, void* stream) {

@@ -70,6 +70,10 @@ int ina_launch_attention_prefix(const void* Q, long q_ps, long q_rs, long q_hs, 
                                 const void* Vc, long c_ss, long c_rs, long c_hs, int n_slots, const void* Ks, const void* Vs, long s_ps, long s_rs,
                                 long s_hs, const int32_t* slot, const int32_t* pfx_len, const int32_t* suf_len, int P, int m, int H, int Hkv, int D,
                                 int max_pfx, float scale, hipStream_t stream);                                               // attention_prefix.hip
+int ina_launch_attention_shared(const void* Q, long q_rs, long q_hs, void* O, long o_rs, long o_hs, const void* Kc, const void* Vc, long c_ss,
+                                long c_rs, long c_hs, int n_slots, const void* Kt, const void* Vt, long t_ps, long t_rs, long t_hs, int T,
+                                const int32_t* tile_rows, const int32_t* tile_slot, const int32_t* tile_pfx, const int32_t* tail_len, int n_tiles,
+                                int n_rows, int H, int Hkv, int D, int max_pfx, float scale, hipStream_t stream);            // attention_shared.hip
 int ina_launch_memory_gather(void* out, long out_env_stride, float* ring, const float* fresh, const float* blank, const float* pe,
                              const int32_t* env, const int32_t* head, const int32_t* count, int n, int max_envs, int M, int ntok, int C, int depth,
                              int stride, hipStream_t stream);                                                                // memory_gather.hip

@@ -9,6 +9,7 @@ import contextlib
 import ctypes as C
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -396,6 +397,66 @@ def attention_prefix(q: torch.Tensor, k_suf: torch.Tensor, v_suf: torch.Tensor, 
                                          pfx_len.data_ptr(), suf_len.data_ptr(), P, m, H, Hkv, D, max_pfx,
                                          float(scale) if scale is not None else float(D) ** -0.5, _stream())
     _lib.check(rc, "attention_prefix")
+    return out
+
+
+ATTN_SHARED_MAX_GROUP = 16    # query heads per KV head of ops.attention_shared (one candidate's heads fill a 16-row tile at most)
+
+
+def attention_shared_plan(prompt_of, G: int):
+    """host tile plan of ops.attention_shared: prompt_of int [R] (the prompt of every row) -> (tile_rows int32 [n_tiles, cpt], tile_prompt
+    int64 [n_tiles]), cpt = 16 // G. The rows of a prompt, in row order, fill tiles of cpt places; a prompt's last tile keeps -1 in the
+    places it cannot fill (rows of two prompts never share a tile: a tile reads ONE prompt's prefix)."""
+    if not 1 <= G <= ATTN_SHARED_MAX_GROUP:
+        raise ValueError(f"attention_shared: {G} query heads per KV head (1 .. {ATTN_SHARED_MAX_GROUP})")
+    cpt = 16 // G
+    prompt_of = np.asarray(prompt_of, dtype=np.int64).reshape(-1)
+    tiles, owner = [], []
+    for b in dict.fromkeys(prompt_of.tolist()):                   # prompts in order of first appearance
+        rows = np.nonzero(prompt_of == b)[0]
+        for i in range(0, rows.size, cpt):
+            t = np.full(cpt, -1, dtype=np.int32)
+            t[: min(cpt, rows.size - i)] = rows[i:i + cpt]
+            tiles.append(t)
+            owner.append(b)
+    return np.stack(tiles) if tiles else np.zeros((0, cpt), dtype=np.int32), np.asarray(owner, dtype=np.int64)
+
+
+def attention_shared(q: torch.Tensor, k_tail: torch.Tensor, v_tail: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                     tile_rows: torch.Tensor, tile_slot: torch.Tensor, tile_pfx: torch.Tensor, tail_len: torch.Tensor,
+                     out: Optional[torch.Tensor] = None, scale: Optional[float] = None, max_pfx: Optional[int] = None) -> torch.Tensor:
+    """single-token attention of R rows whose prompts stay once in a KV cache (ina_attention_shared): row r of tile t sees rows
+    [0, tile_pfx[t]) of cache slot tile_slot[t] and the first tail_len[r] rows of its own tail. Nothing is written to the cache.
+    q [R, H, 128], k_tail / v_tail [R, T, Hkv, 128] (equal strides), k_cache / v_cache [slots, S, Hkv, 128] (equal strides), all bf16 with a
+    contiguous last dim; tile_rows int32 [n_tiles, 16 // (H // Hkv)] (`attention_shared_plan`; -1 = empty place), tile_slot / tile_pfx int32
+    [n_tiles], tail_len int32 [R], all on the device. max_pfx (default S): the largest tile_pfx (longer ones are clipped).
+    A row with tail_len <= 0 comes out as zeros, a slot outside the cache as NaN rows; rows no tile names are not written."""
+    assert q.dtype == k_tail.dtype == v_tail.dtype == k_cache.dtype == v_cache.dtype == torch.bfloat16
+    assert q.dim() == 3 and k_tail.dim() == 4 and k_cache.dim() == 4
+    R, H, D = q.shape
+    T, Hkv = k_tail.shape[1], k_tail.shape[2]
+    n_slots, S = k_cache.shape[0], k_cache.shape[1]
+    assert D == 128, f"attention_shared: head dim {D} (128 only)"
+    assert Hkv > 0 and H % Hkv == 0 and H // Hkv <= ATTN_SHARED_MAX_GROUP, f"attention_shared: {H} heads over {Hkv} KV heads"
+    cpt = 16 // (H // Hkv)
+    assert R >= 1 and T >= 1 and k_tail.shape == (R, T, Hkv, D) and v_tail.shape == k_tail.shape and k_tail.stride() == v_tail.stride()
+    assert k_cache.shape == (n_slots, S, Hkv, D) and v_cache.shape == k_cache.shape and k_cache.stride() == v_cache.stride() and n_slots >= 1
+    if out is None:
+        out = torch.empty(R, H, D, dtype=torch.bfloat16, device=q.device)
+    assert out.shape == q.shape and out.dtype == torch.bfloat16
+    assert all(t.stride(-1) == 1 for t in (q, k_tail, v_tail, k_cache, v_cache, out))
+    n_tiles = tile_rows.shape[0]
+    assert n_tiles >= 1 and tile_rows.shape == (n_tiles, cpt), f"attention_shared: tile table {tuple(tile_rows.shape)} ([n_tiles, {cpt}])"
+    for t, n in ((tile_rows, n_tiles * cpt), (tile_slot, n_tiles), (tile_pfx, n_tiles), (tail_len, R)):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n and t.device == q.device
+    max_pfx = S if max_pfx is None else int(max_pfx)
+    assert 0 <= max_pfx <= S, f"attention_shared: max_pfx={max_pfx} outside the cache's {S} rows per slot"
+    rc = _lib.lib().ina_attention_shared(q.data_ptr(), q.stride(0), q.stride(1), out.data_ptr(), out.stride(0), out.stride(1), k_cache.data_ptr(),
+                                         v_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), n_slots, k_tail.data_ptr(),
+                                         v_tail.data_ptr(), k_tail.stride(0), k_tail.stride(1), k_tail.stride(2), T, tile_rows.data_ptr(),
+                                         tile_slot.data_ptr(), tile_pfx.data_ptr(), tail_len.data_ptr(), n_tiles, R, H, Hkv, D, max_pfx,
+                                         float(scale) if scale is not None else float(D) ** -0.5, _stream())
+    _lib.check(rc, "attention_shared")
     return out
 
 

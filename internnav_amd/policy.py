@@ -451,7 +451,8 @@ class InternVLAN1ForCausalLM:
                  decode_chunk: int = 8, eos_token_id=None, cached_image_embeds: Optional[list] = None, prefix_kv: Optional[list] = None,
                  export_prefix: Optional[list] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
                  temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                 num_return_sequences: Optional[int] = None, generator: Optional[torch.Generator] = None, seed: Optional[int] = None, **kw):
+                 num_return_sequences: Optional[int] = None, generator: Optional[torch.Generator] = None, seed: Optional[int] = None,
+                 share_prefix: bool = False, **kw):
         """greedy decoding by default (do_sample=False is the only mode the reference uses, internvla_n1_policy.py:169-176). Decodes in chunks of
         `decode_chunk` device-side steps and stops once every sequence has emitted EOS. Sequences are right-filled with EOS.
         repetition_penalty / eos_token_id: None = the checkpoint's generation_config.json (`self.generation_config`; without that file 1.0
@@ -488,12 +489,27 @@ class InternVLAN1ForCausalLM:
         reference-signature re-run path (the cached state is of B * K rows). output_logprobs under sampling works on every model
         (token_logprobs=True is not needed: the sampling path keeps its own buffer): token_logprobs = log q of each draw, the log-softmax
         of HF's processed scores (after penalty, temperature, top-k, top-p); token_margins is not defined for a draw and is NaN inside
-        the answer (0.0 behind EOS, like every masked position); answer_confidences' margin of a sampled row is NaN accordingly."""
+        the answer (0.0 behind EOS, like every masked position); answer_confidences' margin of a sampled row is NaN accordingly.
+        share_prefix=True (opt-in, needs do_sample=True, any num_return_sequences K >= 1; without it every launch is what it was): the K
+        answers of a prompt are decoded behind the prompt's ONE cache slot - no replication into K slots, the attention of the single-token
+        passes (ops.attention_shared) reads the prompt in place and every returned sequence keeps only its own answer tokens' K/V in a small
+        tail. Capacity then reads B <= max_seqs and B * K <= 64 (SKINNY_GEMM_MAX_ROWS: the passes stay on the weight-streaming kernels),
+        max_new_tokens <= max_decode; CapacityError before anything is launched. The tokens are not bit-equal to the fan-out path's (another
+        attention kernel: an equally valid rounding). Everything else is as with K > 1 above, for every K: EOS handling, answer_lengths,
+        output_logprobs, seed= / generator=, decode_chunk, past_key_values=None in the result, export_prefix refused, generate_latents on a
+        returned row re-runs it. The prompts' cache slots hold exactly what the prefill wrote when the call returns."""
         smp = sampling_spec(self.generation_config, do_sample, temperature, top_k, top_p, num_return_sequences, kw)
+        if share_prefix and smp is None:
+            raise ValueError("share_prefix=True needs do_sample=True: greedy decoding returns one sequence per prompt and has nothing to share")
         if smp is not None:
-            if smp.K > 1 and export_prefix is not None and any(export_prefix):
-                raise ValueError("export_prefix is not supported with num_return_sequences > 1: export the prefix from a call with one sequence per prompt")
-            if input_ids.shape[0] * smp.K > self.qwen.B_max:
+            if (smp.K > 1 or share_prefix) and export_prefix is not None and any(export_prefix):
+                raise ValueError("export_prefix is not supported with num_return_sequences > 1 or share_prefix=True: export the prefix from a call "
+                                 "with one sequence per prompt")
+            if share_prefix:
+                if input_ids.shape[0] > self.qwen.B_max or input_ids.shape[0] * smp.K > SKINNY_GEMM_MAX_ROWS:
+                    raise CapacityError(f"{input_ids.shape[0]} prompts x num_return_sequences={smp.K} behind shared prompts exceed the engine's "
+                                        f"max_seqs={self.qwen.B_max} prompts or the {SKINNY_GEMM_MAX_ROWS} rows of a single-token pass")
+            elif input_ids.shape[0] * smp.K > self.qwen.B_max:
                 raise CapacityError(f"{input_ids.shape[0]} prompts x num_return_sequences={smp.K} exceed the engine's max_seqs={self.qwen.B_max}")
             if max_new_tokens > self.qwen.max_decode:
                 raise CapacityError(f"max_new_tokens={max_new_tokens} exceeds the max_decode={self.qwen.max_decode} log-probability columns of the "
@@ -539,7 +555,7 @@ class InternVLAN1ForCausalLM:
                 keep = [pv[off[i]:off[i + 1]] for i, s in enumerate(skip) if not s]
                 pv = torch.cat(keep, 0) if keep else None
         state = self.qwen.prefill(input_ids, pv, image_grid_thw, cached_embeds=cached_image_embeds, seq_lens=plens if attention_mask is not None else None,
-                                  prefix_len=pl, **({} if penalty == 1.0 else {"repetition_penalty": penalty}), **self._sampling_kw(smp, B, max_new_tokens, generator, seed))
+                                  prefix_len=pl, **({} if penalty == 1.0 else {"repetition_penalty": penalty}), **self._sampling_kw(smp, B, max_new_tokens, generator, seed, share_prefix))
         self._prefix_out = {}
         if export_prefix is not None:
             for b, n in enumerate(export_prefix):
@@ -563,11 +579,12 @@ class InternVLAN1ForCausalLM:
             toks[b, e:] = eos
             lens.append(e)
         K = 1 if smp is None else smp.K
+        fanned = K > 1 or share_prefix                            # the cached state is of B * K rows (or, shared, of rows without a slot)
         ids_cpu = input_ids.cpu().long()
         if K > 1:                                                 # rows are prompt-major from here on: row b * K + c = prompt b, sequence c
             plens, ids_cpu = np.repeat(plens, K), ids_cpu.repeat_interleave(K, dim=0)
         # (K > 1: the cached state is of B * K rows and a caller continues ONE returned row: generate_latents re-runs it, the reference signature)
-        self._gen = dict(state=state, tokens=toks, lens=np.asarray(lens), prompt_lens=plens) if K == 1 else None
+        self._gen = dict(state=state, tokens=toks, lens=np.asarray(lens), prompt_lens=plens) if not fanned else None
         # every row = its own prompt, then its answer, right-filled with EOS to the common width S + n
         seqs = torch.full((B * K, S + toks.shape[1]), eos, dtype=torch.long)
         for b in range(B * K):
@@ -590,10 +607,10 @@ class InternVLAN1ForCausalLM:
         # a real prompt: only the rows it took from a cache are exact
         exact = int(state["S_run"]) >= ATTN_WIDE_MIN_ROWS and B * int(state["S_run"]) > SKINNY_GEMM_MAX_ROWS
         keep = plens if exact else np.broadcast_to(np.asarray(pl, dtype=np.int64), (B,))
-        pkv = self.qwen.kv_handle([ids_cpu[b, : int(keep[b])] for b in range(B)]) if use_cache and K == 1 else None
+        pkv = self.qwen.kv_handle([ids_cpu[b, : int(keep[b])] for b in range(B)]) if use_cache and not fanned else None
         return SimpleNamespace(sequences=seqs, past_key_values=pkv, **lp_out)
 
-    def _sampling_kw(self, smp, B: int, max_new_tokens: int, generator, seed) -> dict:
+    def _sampling_kw(self, smp, B: int, max_new_tokens: int, generator, seed, share_prefix: bool = False) -> dict:
         """the engine's sampling spec of one generate() call ({} = greedy): the uniforms of every step and returned sequence, drawn HERE on
         the host (one f32 [max_new_tokens, B * K] table, one copy to the device) - no random number is generated in a kernel"""
         if smp is None:
@@ -602,7 +619,8 @@ class InternVLAN1ForCausalLM:
             assert isinstance(generator, torch.Generator) and generator.device.type == "cpu", "generator: a CPU torch.Generator"
         gen = generator if generator is not None else (torch.Generator(device="cpu").manual_seed(int(seed)) if seed is not None else self._sample_gen)
         u = torch.rand(max_new_tokens, B * smp.K, generator=gen, dtype=torch.float32).to(self.device)
-        return {"sampling": dict(temperature=smp.temperature, top_k=smp.top_k, top_p=smp.top_p, u=u, K=smp.K)}
+        # (share_prefix travels beside the spec: `sampling_spec`'s namespace is HF's sampling parameters only)
+        return {"sampling": dict(temperature=smp.temperature, top_k=smp.top_k, top_p=smp.top_p, u=u, K=smp.K, **({"share_prefix": True} if share_prefix else {}))}
 
     def score_answers(self, input_ids, answers, pixel_values=None, image_grid_thw=None, attention_mask=None, share_prefix: bool = False,
                       max_suffix_rows: Optional[int] = None) -> SimpleNamespace:

@@ -26,6 +26,7 @@ HBM layout (B sequences of S tokens, cache capacity S_max, H = 3584):
 from __future__ import annotations
 
 import weakref
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -408,6 +409,9 @@ class QwenVLEngine:
         self.token_logprobs, self.max_decode = bool(token_logprobs), int(max_decode)
         self._lp_steps = self._mg_steps = self.tok_logprob = self.tok_margin = None      # (no buffer at all without the setting)
         self._smp_lp = None      # sampling (prefill(sampling=)): log-probability of the draws, step-major f32 [max_decode, max_seqs], allocated by the first sampling call
+        # shared-prompt sampling (prefill(sampling=dict(share_prefix=True))): row-count-sized twins of logits / next_tok / seen / xl / hl / _smp_lp
+        # and the per-layer answer tails, allocated by the first such call (`_shared_buffers`)
+        self._shared = None
         if self.token_logprobs:
             self._lp_steps, self._mg_steps = (torch.zeros(self.max_decode, max_seqs, dtype=f32, device=dev) for _ in range(2))
             self.tok_logprob, self.tok_margin = self._lp_steps.t(), self._mg_steps.t()
@@ -440,6 +444,7 @@ class QwenVLEngine:
             t.tok_logprob, t.tok_margin = t._lp_steps.t(), t._mg_steps.t()
         t.layers = [dict(L, kv=torch.empty_like(L["kv"])) for L in self.layers]
         t._side = None
+        t._shared = None
         t._kv_reset_tracking()
         return t
 
@@ -620,7 +625,10 @@ class QwenVLEngine:
         if pfx is not None:
             k4 = qkv[:, nh * hd:(nh + nkv) * hd].view(B, S, nkv, hd)
             v4 = qkv[:, (nh + nkv) * hd:].view(B, S, nkv, hd)
-        fuse_rope = pfx is None and single and self.fuse_decode_rope and ph.get("new_are_last", False) and ops.attention_rope_ok(S, ph["Lk"], nh, nkv, hd)
+        # shared-prompt decode pass (ph["shared"], `_shared_phase`): one row per returned sequence; k|v of the new token go to the row's own tail
+        # (the same rope launch, another destination), ops.attention_shared reads the prompt in place; nothing of the cache is written
+        shr = ph.get("shared")
+        fuse_rope = pfx is None and shr is None and single and self.fuse_decode_rope and ph.get("new_are_last", False) and ops.attention_rope_ok(S, ph["Lk"], nh, nkv, hd)
         if fuse_rope:
             kn4 = qkv[:, nh * hd:(nh + nkv) * hd].view(B, S, nkv, hd)
             vn4 = qkv[:, (nh + nkv) * hd:].view(B, S, nkv, hd)
@@ -640,6 +648,13 @@ class QwenVLEngine:
                 kvc = L["kv"].view(self.B_max, Smax, 2, nkv, hd)
                 ops.attention_prefix(q4, k4, v4, kvc[:, :, 0], kvc[:, :, 1], pfx["slot"], pfx["pfx_len"], pfx["suf_len"],
                                      out=att.view(B, S, nh, hd), max_pfx=pfx["max_pfx"])
+            elif shr is not None:
+                tail = shr["tails"][li]
+                ops.rope(qkv, cos, sin, heads=nh + nkv, D=hd, col0=0, rows=rows, kv_out=tail, kv_dst=shr["kv_dst"], kv_head0=nh, v_heads=nkv)
+                kvc = L["kv"].view(self.B_max, Smax, 2, nkv, hd)
+                t5 = tail[: rows * shr["T"]].view(rows, shr["T"], 2, nkv, hd)
+                ops.attention_shared(qkv[:, : nh * hd].view(rows, nh, hd), t5[:, :, 0], t5[:, :, 1], kvc[:, :, 0], kvc[:, :, 1], shr["tile_rows"],
+                                     shr["tile_slot"], shr["tile_pfx"], shr["tail_len"], out=att.view(rows, nh, hd), max_pfx=shr["max_pfx"])
             else:
                 if not fuse_rope:
                     # m-rope on q (in place) and k, and the KV-cache append (rotated k | v -> cache row of every token) in ONE launch
@@ -692,38 +707,41 @@ class QwenVLEngine:
         return self.x[: P * m]
 
     def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None, penalty: Optional[float] = None, col: int = 0,
-                     sampling: Optional[dict] = None, src: Optional[torch.Tensor] = None):
+                     sampling: Optional[dict] = None, src: Optional[torch.Tensor] = None, bufs=None):
         """final RMSNorm + lm_head on ONE row per sequence, greedy argmax on the device. row_in_seq: the same row for every sequence,
         or (ragged batches) rows_idx int32 [B] = absolute row of each sequence's last real token. penalty: the selection runs over the
         repetition-penalised logits of the tokens in `seen` and marks the chosen one (`logits` keeps the raw values).
         col (token_logprobs engines): the answer position this selection produces = the column of tok_logprob / tok_margin it fills.
         sampling (state["sampling"]): ops.sample_rows IN PLACE of the argmax / logprob launch - temperature, top-k, top-p and the draw against
         row `col` of the state's uniform table; the draw's log-probability goes to column col of the sampling buffer. src int32 [B * K]: the
-        output rows (one per returned sequence, with its own seen set) read the B logits rows through it."""
+        output rows (one per returned sequence, with its own seen set) read the B logits rows through it.
+        bufs: the buffer set of the selection - logits, next_tok, seen, xl, hl, _smp_lp; None = the engine's own (sized by max_seqs), else the
+        row-count-sized twins of the shared-prompt path (`_shared_buffers`)."""
+        bf = self if bufs is None else bufs
         if rows_idx is not None:
-            ops.gather_rows(self.x[: B * S], self.xl[:B], src=rows_idx)
-            ops.norm(self.xl[:B], self.norm_w, None, eps=1e-6, rms=True, out=self.hl[:B], rows=B)
+            ops.gather_rows(self.x[: B * S], bf.xl[:B], src=rows_idx)
+            ops.norm(bf.xl[:B], self.norm_w, None, eps=1e-6, rms=True, out=bf.hl[:B], rows=B)
         else:
-            ops.norm(self.x[: B * S], self.norm_w, None, eps=1e-6, rms=True, out=self.hl[:B], rows=B, in_map=(1, S, row_in_seq))
+            ops.norm(self.x[: B * S], self.norm_w, None, eps=1e-6, rms=True, out=bf.hl[:B], rows=B, in_map=(1, S, row_in_seq))
         if (self.w8_decode or self.mx4_decode) and B <= SKINNY_GEMM_MAX_ROWS:
-            ops.linear_w8(self.hl[:B], *self.lm_head8, out=self.logits[:B])
+            ops.linear_w8(bf.hl[:B], *self.lm_head8, out=bf.logits[:B])
         else:
-            ops.linear(self.hl[:B], self.lm_head, out=self.logits[:B])     # (152064 columns: one wave per 16-column tile owns all of K)
+            ops.linear(bf.hl[:B], self.lm_head, out=bf.logits[:B])     # (152064 columns: one wave per 16-column tile owns all of K)
         if sampling is not None:
             R = B if src is None else src.numel()
-            assert col < sampling["u"].shape[0] and col < self._smp_lp.shape[0] and R <= sampling["u"].shape[1], (col, R, sampling["u"].shape)
-            ops.sample_rows(self.logits[:B], sampling["u"][col, :R], self.next_tok[:R], self._smp_lp[col, :R], temperature=sampling["temperature"],
-                            top_k=sampling["top_k"], top_p=sampling["top_p"], seen=None if penalty is None else self.seen,
+            assert col < sampling["u"].shape[0] and col < bf._smp_lp.shape[0] and R <= sampling["u"].shape[1], (col, R, sampling["u"].shape)
+            ops.sample_rows(bf.logits[:B], sampling["u"][col, :R], bf.next_tok[:R], bf._smp_lp[col, :R], temperature=sampling["temperature"],
+                            top_k=sampling["top_k"], top_p=sampling["top_p"], seen=None if penalty is None else bf.seen,
                             penalty=1.0 if penalty is None else penalty, mark=penalty is not None, src=src)
         elif self.token_logprobs:
             # the same selection (bit-equal ids) + log-softmax at the chosen index and the top-2 margin, in the launch that replaces the argmax
             assert col < self.max_decode, (col, self.max_decode)     # (plan() / decode() refuse longer answers before anything is launched)
-            ops.logprob_rows(self.logits[:B], self.next_tok[:B], self._lp_steps[col, :B], self._mg_steps[col, :B],
-                             seen=None if penalty is None else self.seen, penalty=1.0 if penalty is None else penalty, mark=penalty is not None)
+            ops.logprob_rows(bf.logits[:B], bf.next_tok[:B], self._lp_steps[col, :B], self._mg_steps[col, :B],
+                             seen=None if penalty is None else bf.seen, penalty=1.0 if penalty is None else penalty, mark=penalty is not None)
         elif penalty is None:
-            ops.argmax_rows(self.logits[:B], self.next_tok[:B])
+            ops.argmax_rows(bf.logits[:B], bf.next_tok[:B])
         else:
-            ops.argmax_penalty_rows(self.logits[:B], self.seen, penalty, self.next_tok[:B], mark=True)
+            ops.argmax_penalty_rows(bf.logits[:B], bf.seen, penalty, bf.next_tok[:B], mark=True)
 
     def last_logprobs(self, state: dict):
         """(logprob, margin) f32 [B, n] device views: one value per answer token selected so far from `state` (what `prefill` returned and
@@ -740,7 +758,8 @@ class QwenVLEngine:
         """f32 [rows, n] device view: log q of every token drawn so far from a sampling `state` (rows = B * num_return_sequences), the
         log-softmax of HF's processed scores (penalty, temperature, top-k, top-p) at the draw. A view: the next sampling call overwrites it."""
         assert "sampling" in state, "not a sampling state (prefill(..., sampling=...))"
-        return self._smp_lp.t()[: state["B"], : int(state.get("n_sel", 0))]
+        lp = self._shared._smp_lp if state["sampling"].get("share_prefix") else self._smp_lp
+        return lp.t()[: state["B"], : int(state.get("n_sel", 0))]
 
     def _fan_out(self, state: dict, K: int):
         """num_return_sequences = K behind ONE prefill: the prompt rows of cache slot b go to slots b * K + c (ina_kv_copy, out to temporary
@@ -759,6 +778,55 @@ class QwenVLEngine:
             state["lens"] = np.repeat(n, K)
             state["cur"] = state["lens"].copy()
         state["fan"] = K
+
+    def _shared_buffers(self, rows: int, T: int) -> SimpleNamespace:
+        """the buffers of the shared-prompt sampling path, sized by its ROW count (returned sequences), not by max_seqs: twins of logits /
+        next_tok / seen / xl / hl / _smp_lp (what a selection step touches, `_last_logits(bufs=)`) and per layer a tail [rows * T, 2 * Hkv * hd]
+        in the cache's row format (row r keeps the k|v of its answer token t at tail row r * T + t). Allocated by the first shared call, grown
+        only when a later call needs more rows or a longer answer (T <= max_decode); an engine that never takes the path allocates nothing."""
+        sh = self._shared
+        if sh is not None and sh.rows >= rows and sh.T >= T:
+            return sh
+        rows, T = max(rows, sh.rows if sh else 0), max(T, sh.T if sh else 0)
+        self._shared = sh = None                                  # (the old set goes before the new one comes)
+        dev, bf, f32 = self.device, torch.bfloat16, torch.float32
+        self._shared = SimpleNamespace(
+            rows=rows, T=T, logits=torch.empty(rows, self.cfg["vocab"], dtype=f32, device=dev), next_tok=torch.empty(rows, dtype=torch.int32, device=dev),
+            seen=torch.zeros(rows, self.seen.shape[1], dtype=torch.uint32, device=dev), xl=torch.empty(rows, self.H, dtype=f32, device=dev),
+            hl=torch.empty(rows, self.H, dtype=bf, device=dev), _smp_lp=torch.zeros(T, rows, dtype=f32, device=dev),
+            tails=[torch.empty(rows * T, self.kv_w, dtype=bf, device=dev) for _ in self.layers])
+        return self._shared
+
+    def _share_out(self, state: dict, K: int):
+        """num_return_sequences = K behind ONE prefill WITHOUT a cache slot per returned sequence (sampling spec share_prefix): `state` becomes
+        the decode state of B * K rows (prompt-major, next_pos / lens / cur replicated as `_fan_out` replicates them); row b * K + c keeps
+        reading prompt b in cache slot b (pfx_len = the prompt's length) and appends its own answer tokens to its tail (tail_len = 0 here).
+        Host work only: the tile table of ops.attention_shared (rows of one prompt share a tile) and its per-tile slot / length."""
+        B, lens = state["B"], state.get("lens")
+        n = np.full(B, state["S"], dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64)
+        prompt_of = np.repeat(np.arange(B), K)
+        tiles, owner = ops.attention_shared_plan(prompt_of, self.nh // self.nkv)
+        i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(self.device)
+        state["shared"] = dict(slot=prompt_of, pfx_len=n[prompt_of], tail_len=0, tile_rows=i32(tiles), tile_slot=i32(owner), tile_pfx=i32(n[owner]),
+                               max_pfx=int(n.max()))
+        state["B"] = B * K
+        state["next_pos"] = np.repeat(np.asarray(state["next_pos"]), K)
+        if lens is not None:
+            state["lens"] = np.repeat(n, K)
+            state["cur"] = state["lens"].copy()
+        state["fan"] = K
+
+    def _shared_phase(self, state: dict) -> dict:
+        """host side of one single-token pass of the shared-prompt path: every row runs its pending token at text position next_pos, appends
+        its k|v at tail row tail_len (all rows advance together) and attends its prompt + tail_len + 1 tail rows"""
+        sh, bufs, R = state["shared"], self._shared, state["B"]
+        t = int(sh["tail_len"])
+        assert t < bufs.T and R <= bufs.rows, (t, bufs.T, R, bufs.rows)
+        i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(self.device)
+        pos = np.broadcast_to(np.asarray(state["next_pos"], dtype=np.int64).reshape(1, R), (3, R))
+        return dict(B=R, S=1, pos=i32(pos), b0=0, r0=0,
+                    shared=dict(tails=bufs.tails, T=bufs.T, kv_dst=i32(np.arange(R) * bufs.T + t), tail_len=i32(np.full(R, t + 1)),
+                                tile_rows=sh["tile_rows"], tile_slot=sh["tile_slot"], tile_pfx=sh["tile_pfx"], max_pfx=sh["max_pfx"]))
 
     def _seen_init(self, P: dict):
         """launch in front of a decode's first selection: every sequence's seen set = its whole prompt (cached prefix included)"""
@@ -1120,6 +1188,10 @@ class QwenVLEngine:
         engine without token_logprobs=True samples as well (`last_sample_logprobs`). K > 1: the B prompts are prefilled once (images encoded
         once), the K first tokens of prompt b are drawn from its ONE logits row, its cache rows are replicated into slots b * K + c
         (`_fan_out`) and decoding continues with B * K rows, prompt-major; B * K > max_seqs raises CapacityError before anything is launched.
+        share_prefix=True in the dict (opt-in, any K >= 1): no fan-out - the prompts stay in their B slots, which nothing writes after the
+        prefill; row b * K + c appends the k|v of its answer tokens to a small tail of its own and ops.attention_shared reads prompt b in
+        place (`_share_out`). The selection runs on row-count-sized twins of the max_seqs-sized buffers (`_shared_buffers`, allocated by the
+        first such call). Capacity: B <= max_seqs and B * K <= SKINNY_GEMM_MAX_ROWS, else CapacityError before anything is launched.
         plan() / run_decode (the graph path) stay greedy."""
         if sampling is not None:
             sampling = self._sampling_state(sampling, input_ids.shape[0])
@@ -1137,12 +1209,23 @@ class QwenVLEngine:
         T, top_k, top_p, u = float(spec["temperature"]), int(spec.get("top_k", 0) or 0), float(spec.get("top_p", 1.0)), spec["u"]
         if K < 1 or not (np.isfinite(T) and T > 0.0) or top_k < 0 or not 0.0 < top_p <= 1.0:
             raise ValueError(f"sampling spec: temperature={T} (> 0), top_k={top_k} (>= 0), top_p={top_p} (in (0, 1]), K={K} (>= 1)")
-        if B * K > self.B_max:
+        share = bool(spec.get("share_prefix", False))
+        if share:
+            if self.hd != 128 or self.nh // self.nkv > ops.ATTN_SHARED_MAX_GROUP:
+                raise ValueError(f"sampling spec: share_prefix needs head dim 128 and at most {ops.ATTN_SHARED_MAX_GROUP} query heads per KV head "
+                                 f"(ops.attention_shared), this model has {self.hd} and {self.nh // self.nkv}")
+            if B > self.B_max or B * K > min(SKINNY_GEMM_MAX_ROWS, self.x.shape[0]):
+                raise CapacityError(f"{B} prompts x {K} returned sequences behind shared prompts exceed max_seqs={self.B_max} prompts or "
+                                    f"{min(SKINNY_GEMM_MAX_ROWS, self.x.shape[0])} rows (the single-token passes stay on the weight-streaming kernels)")
+        elif B * K > self.B_max:
             raise CapacityError(f"{B} prompts x {K} returned sequences exceed the engine's max_seqs={self.B_max}")
         if not (u.dtype == torch.float32 and u.dim() == 2 and u.shape[1] == B * K and u.is_contiguous() and u.device == self.device):
             raise ValueError(f"sampling spec: u must be a contiguous f32 [steps, {B * K}] tensor on {self.device}")
         if u.shape[0] > self.max_decode:
             raise CapacityError(f"{u.shape[0]} sampling steps exceed the engine's max_decode={self.max_decode} log-probability columns")
+        if share:
+            self._shared_buffers(B * K, int(u.shape[0]))
+            return dict(temperature=T, top_k=top_k, top_p=top_p, u=u, K=K, share_prefix=True)
         if self._smp_lp is None:
             self._smp_lp = torch.zeros(self.max_decode, self.B_max, dtype=torch.float32, device=self.device)
         return dict(temperature=T, top_k=top_k, top_p=top_p, u=u, K=K)
@@ -1171,7 +1254,10 @@ class QwenVLEngine:
         Sr = state.get("S_run", S)                                # rows per sequence in x (prompt minus a cached prefix)
         smp = state.get("sampling")                               # None: greedy
         K = smp["K"] if smp is not None and "cur" not in state else 1      # > 1: this call makes the first draw and fans the batch out
-        out = torch.empty(B * K, n_steps, dtype=torch.int32, device=self.device)
+        share = smp is not None and smp.get("share_prefix", False)         # shared prompts: no fan-out, the twins of the selection buffers
+        bufs = self._shared if share else None
+        nt = bufs.next_tok if share else self.next_tok
+        out =torch.empty(B * K, n_steps, dtype=torch.int32, device=self.device)
         lens = state.get("lens")
         pen = state["plan"].get("rep_penalty")
         if smp is not None and state.get("n_sel", 1) + n_steps - 1 > smp["u"].shape[0]:          # before anything is launched
@@ -1183,11 +1269,13 @@ class QwenVLEngine:
             if pen is not None:
                 self._seen_init(state["plan"])
             kw = {} if smp is None else {"sampling": smp}
-            if K > 1:
+            if share:
+                kw["bufs"] = bufs
+            if K > 1 or share:
                 kw["src"] = torch.arange(B, dtype=torch.int32, device=self.device).repeat_interleave(K)
                 if pen is not None:                               # one seen set per returned sequence: the draw marks row b * K + c
                     bits = self.seen.view(torch.int32)
-                    bits[: B * K].copy_(bits[:B].repeat_interleave(K, dim=0))
+                    (bufs.seen.view(torch.int32) if share else bits)[: B * K].copy_(bits[:B].repeat_interleave(K, dim=0))
             if lens is None and bool((state["plan"]["prefix_len"] == state["plan"]["prefix_len"][0]).all()):
                 self._last_logits(B, Sr, Sr - 1, penalty=pen, col=0, **kw)
                 state["cur"] = S
@@ -1200,20 +1288,26 @@ class QwenVLEngine:
                 self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen, col=0, **kw)
                 state["cur"] = lens.copy()
             state["n_sel"] = 1                                    # selections made so far = answer tokens with a log-probability column
-            if K > 1:
+            if share:
+                self._share_out(state, K)
+                B, lens = state["B"], state.get("lens")
+            elif K > 1:
                 self._fan_out(state, K)
                 B, lens = state["B"], state.get("lens")
         for j in range(n_steps):
-            out[:, j].copy_(self.next_tok[:B])
+            out[:, j].copy_(nt[:B])
             if j == n_steps - 1:
                 break
             cur = state["cur"]
-            ops.gather_rows(self.embed, self.x_in, src=self.next_tok[:B], rows=B)
-            if lens is None:
+            ops.gather_rows(self.embed, self.x_in, src=nt[:B], rows=B)
+            if share:
+                self._layers(self._shared_phase(state))
+                state["shared"]["tail_len"] += 1
+            elif lens is None:
                 self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur))
             else:
                 self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur, k_len=cur + 1))
-            self._last_logits(B, 1, 0, penalty=pen, col=state["n_sel"], **({} if smp is None else {"sampling": smp}))
+            self._last_logits(B, 1, 0, penalty=pen, col=state["n_sel"], **({} if smp is None else {"sampling": smp}), **({"bufs": bufs} if share else {}))
             state["n_sel"] += 1
             state["cur"] = cur + 1
             state["next_pos"] = state["next_pos"] + 1
