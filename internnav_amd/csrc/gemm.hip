@@ -185,7 +185,7 @@ int ina_plan_gemm(const GemmArgs& p_in, GemmArgs& p, int& kernel) {
     INA_REQUIRE(!p.glu || !p.R, "gemm: glu cannot be combined with a residual (R)");
     INA_REQUIRE(!p.glu || !p.colscale, "gemm: glu cannot be combined with colscale");
     // tile selection: big tiles when the grid still fills the 256 CUs, smaller ones otherwise
-    // skinny M: HBM-bound weight streaming with split-K (gemm_skinny.hip) instead of an under-filled tile grid
+    // skinny M: HBM-bound weight streaming (gemm_skinny.hip) instead of an under-filled tile grid
     INA_REQUIRE(!p.seg_stats || (p.M > 64 && !p.norm_gamma), "gemm: seg_stats exist in the row-panel kernels only (M >= 16384 rows; M=%d)", p.M);
     if (p.norm_gamma) {
         INA_REQUIRE(p.M <= 16 && p.batch <= 1 && p.K % 8 == 0 && p.K <= 4096 && p.N >= 256,

@@ -43,11 +43,11 @@ using AttnBwdArgs = ina_attn_bwd_args;
 
 int ina_launch_gemm(const GemmArgs& p, hipStream_t stream);
 int ina_plan_gemm(const GemmArgs& p_in, GemmArgs& p, int& kernel);   // validation + kernel selection only (no launch)
-int ina_launch_gemm_skinny_prenorm(const GemmArgs& p, hipStream_t stream);   // M <= 16 with the input RMSNorm fused in front (gemm_skinny.hip)
+int ina_launch_gemm_skinny_prenorm(const GemmArgs& p, hipStream_t stream);   // M <= 16 with the input RMSNorm fused in front (gemm_skinny.hip: the bf16 format of gemm_skinny_core.h)
 int ina_launch_gemm_glds(const GemmArgs& p, hipStream_t stream, int cfg);  // direct-to-LDS staged large-K path
 int ina_launch_gemm_skinny_fused(const GemmArgs& p, hipStream_t stream);  // M <= 64 weight-streaming, workgroup owns its columns for all K, fused epilogue
-int ina_launch_gemm_w8(const GemmArgs& p, const void* W8, const int8_t* wexp, hipStream_t stream);   // gemm_skinny_w8.hip: the weight-streaming kernels on e4m3 weights with a 2^e scale per row
-int ina_launch_gemm_mx4(const GemmArgs& p, const void* W4, const void* wscale, hipStream_t stream);   // gemm_skinny_mx4.hip: the weight-streaming kernels on MXFP4 weights (e2m1 + an e8m0 scale per 32 k)
+int ina_launch_gemm_w8(const GemmArgs& p, const void* W8, const int8_t* wexp, hipStream_t stream);   // gemm_skinny_w8.hip: the weight-streaming kernels (gemm_skinny_core.h) on e4m3 weights with a 2^e scale per row
+int ina_launch_gemm_mx4(const GemmArgs& p, const void* W4, const void* wscale, hipStream_t stream);   // gemm_skinny_mx4.hip: the weight-streaming kernels (gemm_skinny_core.h) on MXFP4 weights (e2m1 + an e8m0 scale per 32 k)
 int ina_launch_gemm_rowpanel(const GemmArgs& p, hipStream_t stream, int cfg);  // gemm_rowpanel.hip: K = 384, register-resident row panels (cfg 34 / 35)
 bool ina_gemm_rowpanel_contract(const GemmArgs& p);
 bool ina_gemm_w4_contract(const GemmArgs& p);

@@ -157,7 +157,7 @@ def test_exact_weight_streaming_wide(ops):
     _exact(ops, G.skinny_wide_cases(DEV))
 
 
-@pytest.mark.parametrize("K", [512, 1024, 4096])
+@pytest.mark.parametrize("K", [136, 512, 520, 1024, 4096])
 def test_exact_fused_input_rmsnorm(ops, K):
     _exact(ops, G.prenorm_cases(K, DEV))
 

@@ -62,7 +62,7 @@ def test_exact_weight_streaming_wide():
     _exact(G.skinny_wide_cases(DEV))
 
 
-@pytest.mark.parametrize("K", [512, 1024, 4096])
+@pytest.mark.parametrize("K", [136, 512, 520, 1024, 4096])
 def test_exact_prenorm(K):
     _exact(G.prenorm_cases(K, DEV))
 
