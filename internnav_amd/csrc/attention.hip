@@ -9,22 +9,13 @@
 //   S^T[kv][q] = K . Q^T   (A operand = K fragment, B operand = Q fragment)  -> lane holds S[q][kv = t*16 + g*4 + r]
 //   O^T[d][q]  = V^T . P^T (A operand = V^T fragment, B operand = P fragment) -> lane holds O[q][d = nt*16 + g*4 + r]
 // P therefore never leaves its lane: the 8 probabilities a lane computed for a 32-key sub-block are exactly its PV B-operand,
-// provided V^T is laid out in LDS with the matching key permutation pos(kv) (see vt_pos below). Softmax statistics are
+// provided V^T is laid out in LDS with the matching key permutation pos(kv) (vt_pos, attention_chunk.h). Softmax statistics are
 // reduced across the 4 lane groups with two xor-shuffles.
+#include "attention_chunk.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace {
-
-// V^T LDS image: row d holds the block's keys in the slot order vt_pos(key), with its 8-slot groups ROTATED by d >> 3 (mod KVB/8).
-// The transposing 2-byte stores of one wave instruction go to rows d = c*8 + i for 8-16 different chunks c: without the rotation
-// all of them fall on the same bank (row stride x 8 = 0 mod 32 dwords), a 16-way conflict on every store.
-__device__ __forceinline__ int vt_pos(int kv_local) {
-    // key permutation inside each 32-key sub-block: MFMA k index g*8 + j  <->  key (j<4 ? g*4+j : 16+g*4+(j-4))
-    int sub = kv_local >> 5, w = kv_local & 31;
-    int t = w >> 4, x = w & 15;
-    return (sub << 5) + ((x >> 2) << 3) + (x & 3) + (t << 2);
-}
 
 template <int DP, int DV, int NW, int KVB, bool DROP = false>
 __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(AttnArgs p) {
@@ -218,11 +209,19 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(AttnArgs p) {
 //     (row R -> head kh*G + R / Lq, position R % Lq), so the K/V of a KV head are read once instead of G times;
 //   * split-KV: grid.x slices the keys in chunks of DEC_CHUNK; each one-wave workgroup writes an un-normalised partial
 //     (O, running max m, running sum l) to a workspace, a second kernel merges the slices (flash-decoding).
-constexpr int DEC_CHUNK = 64;
+// The chunk step of the three kernels below is attention_chunk.h's; each keeps its walk over the chunks, its prologue and its output write.
+constexpr int DEC_CHUNK = AC_KVB;
+
+// the mask of the decode kernels on the key index: packed row (live, position qpos) of a sequence with len_k keys, the Lq query tokens its last
+__device__ __forceinline__ auto dec_mask(const AttnArgs& p, bool live, int qpos, int len_k) {
+    const bool causal = p.causal;
+    const int causal_shift = len_k - p.Lq;
+    return [=](int kv) { return live && (kv < len_k) && (!causal || kv <= qpos + causal_shift); };
+}
 
 template <int DP, int DV>
 __global__ __launch_bounds__(64) void attn_decode_split_kernel(AttnArgs p, float* __restrict__ ws, int nsplit, int rtiles) {
-    constexpr int KVB = 64, KS_LD = DP + 8, VT_LD = KVB + 8, KCPR = DP / 8, VCPR = DV / 8, NKK = DP / 32, NST = KVB / 16, NSB = KVB / 32, NDT = DV / 16;
+    constexpr int KVB = AC_KVB, KS_LD = DP + 8, VT_LD = AC_VT_LD, KCPR = DP / 8, VCPR = DV / 8, NKK = DP / 32, NDT = DV / 16;
     __shared__ __attribute__((aligned(16))) bf16 Ks[KVB * KS_LD];
     __shared__ __attribute__((aligned(16))) bf16 Vt[DV * VT_LD];
     const int lane = threadIdx.x, g = lane >> 4, lq = lane & 15;
@@ -252,91 +251,21 @@ __global__ __launch_bounds__(64) void attn_decode_split_kernel(AttnArgs p, float
         }
         // the whole K / V chunk is requested before the first LDS store: one memory latency per workgroup instead of one per 16-byte
         // piece (this one-wave kernel has nothing else to hide it behind)
-        constexpr int NKI = KVB * KCPR / 64, NVI = KVB * VCPR / 64;
-        static_assert((KVB * KCPR) % 64 == 0 && (KVB * VCPR) % 64 == 0, "chunk pieces must divide evenly over the wave");
-        bf16x8 kreg[NKI], vreg[NVI];
-#pragma unroll
-        for (int u = 0; u < NKI; ++u) {
-            const int q = lane + u * 64, row = q / KCPR, c = q % KCPR, kv = kv0 + row;
-            kreg[u] = (kv < len_k && c * 8 < p.D) ? *reinterpret_cast<const bf16x8*>(K + (size_t)kv * p.k_rs + c * 8) : zero8;
-        }
-#pragma unroll
-        for (int u = 0; u < NVI; ++u) {
-            const int q = lane + u * 64, row = q / VCPR, c = q % VCPR, kv = kv0 + row;
-            vreg[u] = (kv < len_k) ? *reinterpret_cast<const bf16x8*>(V + (size_t)kv * p.v_rs + c * 8) : zero8;
-        }
-#pragma unroll
-        for (int u = 0; u < NKI; ++u) {
-            const int q = lane + u * 64, row = q / KCPR, c = q % KCPR;
-            *reinterpret_cast<bf16x8*>(&Ks[row * KS_LD + c * 8]) = kreg[u];
-        }
-#pragma unroll
-        for (int u = 0; u < NVI; ++u) {
-            const int q = lane + u * 64, row = q / VCPR, c = q % VCPR;
-            const int pos = vt_pos(row);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) Vt[(c * 8 + i) * VT_LD + ((pos + 8 * c) & (KVB - 1))] = vreg[u][i];   // rotated rows: see vt_pos
-        }
+        bf16x8 kreg[KVB * KCPR / 64], vreg[KVB * VCPR / 64];
+        ac_fetch_rows<DP, true>(K, p.k_rs, kv0, len_k, p.D, lane, kreg);
+        ac_fetch_v<DV>(V, p.v_rs, kv0, len_k, lane, vreg);
+        ac_store_k_image<DP>(Ks, lane, kreg);
+        ac_store_vt_image<DV>(Vt, lane, vreg);
         __syncthreads();
-        f32x4 s[NST];
-#pragma unroll
-        for (int t = 0; t < NST; ++t) {
-            s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) {
-                bf16x8 kf = *reinterpret_cast<const bf16x8*>(&Ks[(t * 16 + lq) * KS_LD + kk * 32 + g * 8]);
-                s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], s[t], 0, 0, 0);
-            }
-        }
-        const float sc = p.scale * 1.4426950408889634f;
-        const int causal_shift = len_k - p.Lq;
-        float mx = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < NST; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                int kv = kv0 + t * 16 + g * 4 + r;
-                bool ok = live && (kv < len_k) && (!p.causal || kv <= qpos + causal_shift);
-                float v = ok ? s[t][r] * sc : -INFINITY;
-                s[t][r] = v;
-                mx = fmaxf(mx, v);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        m_run = mx;
-        const float m_use = (mx == -INFINITY) ? 0.f : mx;
-        float rs = 0.f;
-#pragma unroll
-        for (int t = 0; t < NST; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float e = exp2f(s[t][r] - m_use);
-                s[t][r] = e;
-                rs += e;
-            }
-        rs += __shfl_xor(rs, 16);
-        rs += __shfl_xor(rs, 32);
-        l_run = rs;
-#pragma unroll
-        for (int sb = 0; sb < NSB; ++sb) {
-            bf16x8 pf;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                pf[r] = (bf16)s[2 * sb][r];
-                pf[4 + r] = (bf16)s[2 * sb + 1][r];
-            }
-#pragma unroll
-            for (int nt = 0; nt < NDT; ++nt) {
-                bf16x8 vf = *reinterpret_cast<const bf16x8*>(&Vt[(nt * 16 + lq) * VT_LD + ((sb * 32 + g * 8 + 8 * ((nt * 16 + lq) >> 3)) & (KVB - 1))]);
-                acc_o[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, acc_o[nt], 0, 0, 0);
-            }
-        }
+        f32x4 s[AC_NST];
+        ac_scores_image<NKK>(Ks, lq, g, qf, s);
+        // the one-chunk case of the running update: m_run = the chunk's max, l_run = its row sum, nothing to rescale
+        ac_softmax_update(s, kv0, g, p.scale * 1.4426950408889634f, dec_mask(p, live, qpos, len_k), m_run, l_run);
+        bf16x8 pf[AC_NSB];
+        ac_pack_p(s, pf);
+        ac_pv<NDT>(Vt, lq, g, pf, acc_o);
     }
-    // partial: row lq -> [DV] un-normalised O (exp2 domain), then m, l
-    float* orow = out + (size_t)lq * (DV + 2);
-#pragma unroll
-    for (int nt = 0; nt < NDT; ++nt) *reinterpret_cast<f32x4*>(orow + nt * 16 + g * 4) = acc_o[nt];
-    if (g == 0) { orow[DV] = m_run; orow[DV + 1] = l_run; }
+    ac_store_partial<DV + 2>(out, lq, g, acc_o, m_run, l_run);
 }
 
 template <int DV>
@@ -381,15 +310,32 @@ __global__ __launch_bounds__(64) void attn_decode_combine_kernel(AttnArgs p, con
 
 // One-launch variant for key axes of up to DEC_FUSED_MAX_CHUNKS chunks (Lk <= 1024: every decode / latent-query pass of the 4-frame prompt):
 // ONE 4-wave workgroup per (sequence, KV head, row tile). Wave w walks the chunks w, w + 4, ... with a running (max, sum, O) in registers -
-// the chunk body is the split kernel's, on a wave-private LDS image, the next chunk's K / V pieces requested before the current one is
-// multiplied - then the four partials meet in LDS and the workgroup writes the normalised rows itself. 28 workgroups and one launch per
+// the chunk step is the split kernel's (attention_chunk.h), on a wave-private LDS image, the next chunk's K / V pieces requested before the current
+// one is multiplied - then the four partials meet in LDS and the workgroup writes the normalised rows itself. 28 workgroups and one launch per
 // layer instead of 420 + 196 one-wave workgroups in two launches: what the decode chain needs while it shares the CUs with System-1
 // (a launch advances when a System-1 workgroup retires, profiles/r03d_step_breakdown.log).
 constexpr int DEC_FUSED_WAVES = 4, DEC_FUSED_MAX_CHUNKS = 16;
 
+// output of the one-launch kernels: thread tid < 256 combines the NW partials of packed row tid / 16 of row tile rt and writes its DV / 16 columns
+template <int NW, int PER_WAVE, int DV>
+__device__ __forceinline__ void dec_write_rows(const AttnArgs& p, const char* smem, int tid, int kh, int rt, int b) {
+    constexpr int CPT = DV / 16;
+    const int G = p.H / p.Hkv;
+    const int row = tid >> 4, c0 = (tid & 15) * CPT;
+    const int Rr = rt * 16 + row;
+    if (Rr >= G * p.Lq) return;
+    float o[CPT];
+    ac_combine<NW, PER_WAVE, DV + 2, DV>(smem, row, c0, o);
+    const int hd = kh * G + Rr / p.Lq, qp = Rr % p.Lq;
+    bf16* O = reinterpret_cast<bf16*>(p.O) + (size_t)b * p.o_bs + (size_t)qp * p.o_rs + (size_t)hd * p.o_hs;
+#pragma unroll
+    for (int c = 0; c < CPT; ++c)
+        if (c0 + c < p.D) O[c0 + c] = (bf16)o[c];
+}
+
 template <int DP, int DV>
 __global__ __launch_bounds__(DEC_FUSED_WAVES * 64) void attn_decode_fused_kernel(AttnArgs p, int nsplit, int rtiles) {
-    constexpr int KVB = 64, KS_LD = DP + 8, VT_LD = KVB + 8, KCPR = DP / 8, VCPR = DV / 8, NKK = DP / 32, NST = KVB / 16, NSB = KVB / 32, NDT = DV / 16;
+    constexpr int KVB = AC_KVB, KS_LD = DP + 8, VT_LD = AC_VT_LD, KCPR = DP / 8, VCPR = DV / 8, NKK = DP / 32, NDT = DV / 16;
     constexpr int PER_WAVE = KVB * KS_LD + DV * VT_LD;          // bf16 elements of one wave's K image + V^T image
     constexpr int PLD = DV + 2;                                 // partial row: DV x O, m, l (f32)
     static_assert(16 * PLD * 4 <= KVB * KS_LD * 2, "the partial of a wave fits its K image");
@@ -419,142 +365,34 @@ __global__ __launch_bounds__(DEC_FUSED_WAVES * 64) void attn_decode_fused_kernel
         const int d = kk * 32 + g * 8;
         qf[kk] = (live && d < p.D) ? *reinterpret_cast<const bf16x8*>(Q + d) : zero8;
     }
-    constexpr int NKI = KVB * KCPR / 64, NVI = KVB * VCPR / 64;
-    static_assert((KVB * KCPR) % 64 == 0 && (KVB * VCPR) % 64 == 0, "chunk pieces must divide evenly over the wave");
-    bf16x8 kreg[NKI], vreg[NVI];
+    bf16x8 kreg[KVB * KCPR / 64], vreg[KVB * VCPR / 64];
     auto fetch = [&](int kv0) {
-#pragma unroll
-        for (int u = 0; u < NKI; ++u) {
-            const int q = lane + u * 64, row = q / KCPR, c = q % KCPR, kv = kv0 + row;
-            kreg[u] = (kv < len_k && c * 8 < p.D) ? *reinterpret_cast<const bf16x8*>(K + (size_t)kv * p.k_rs + c * 8) : zero8;
-        }
-#pragma unroll
-        for (int u = 0; u < NVI; ++u) {
-            const int q = lane + u * 64, row = q / VCPR, c = q % VCPR, kv = kv0 + row;
-            vreg[u] = (kv < len_k) ? *reinterpret_cast<const bf16x8*>(V + (size_t)kv * p.v_rs + c * 8) : zero8;
-        }
+        ac_fetch_rows<DP, true>(K, p.k_rs, kv0, len_k, p.D, lane, kreg);
+        ac_fetch_v<DV>(V, p.v_rs, kv0, len_k, lane, vreg);
     };
     const float sc = p.scale * 1.4426950408889634f;
-    const int causal_shift = len_k - p.Lq;
+    const auto mask = dec_mask(p, live, qpos, len_k);
     int split = wave;
     if (split * DEC_CHUNK < len_k) fetch(split * DEC_CHUNK);
     for (; split * DEC_CHUNK < len_k; split += DEC_FUSED_WAVES) {
-        const int kv0 = split * DEC_CHUNK;
         // registers -> this wave's LDS images (the reads of the previous chunk were consumed by its MFMAs: the LDS queue of a wave is in order)
-#pragma unroll
-        for (int u = 0; u < NKI; ++u) {
-            const int q = lane + u * 64, row = q / KCPR, c = q % KCPR;
-            *reinterpret_cast<bf16x8*>(&Ks[row * KS_LD + c * 8]) = kreg[u];
-        }
-#pragma unroll
-        for (int u = 0; u < NVI; ++u) {
-            const int q = lane + u * 64, row = q / VCPR, c = q % VCPR;
-            const int pos = vt_pos(row);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) Vt[(c * 8 + i) * VT_LD + ((pos + 8 * c) & (KVB - 1))] = vreg[u][i];   // rotated rows: see vt_pos
-        }
+        ac_store_k_image<DP>(Ks, lane, kreg);
+        ac_store_vt_image<DV>(Vt, lane, vreg);
         if ((split + DEC_FUSED_WAVES) * DEC_CHUNK < len_k) fetch((split + DEC_FUSED_WAVES) * DEC_CHUNK);      // next chunk in flight under this one's math
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        f32x4 s[NST];
-#pragma unroll
-        for (int t = 0; t < NST; ++t) {
-            s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) {
-                bf16x8 kf = *reinterpret_cast<const bf16x8*>(&Ks[(t * 16 + lq) * KS_LD + kk * 32 + g * 8]);
-                s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], s[t], 0, 0, 0);
-            }
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < NST; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kv = kv0 + t * 16 + g * 4 + r;
-                const bool ok = live && (kv < len_k) && (!p.causal || kv <= qpos + causal_shift);
-                const float v = ok ? s[t][r] * sc : -INFINITY;
-                s[t][r] = v;
-                mx = fmaxf(mx, v);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-        const float alpha = (m_run == -INFINITY) ? 0.f : exp2f(m_run - m_use);
-        float rs = 0.f;
-#pragma unroll
-        for (int t = 0; t < NST; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = exp2f(s[t][r] - m_use);
-                s[t][r] = e;
-                rs += e;
-            }
-        rs += __shfl_xor(rs, 16);
-        rs += __shfl_xor(rs, 32);
-        l_run = l_run * alpha + rs;
-        m_run = m_new;
-#pragma unroll
-        for (int nt = 0; nt < NDT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc_o[nt][r] *= alpha;
-#pragma unroll
-        for (int sb = 0; sb < NSB; ++sb) {
-            bf16x8 pf;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                pf[r] = (bf16)s[2 * sb][r];
-                pf[4 + r] = (bf16)s[2 * sb + 1][r];
-            }
-#pragma unroll
-            for (int nt = 0; nt < NDT; ++nt) {
-                bf16x8 vf = *reinterpret_cast<const bf16x8*>(&Vt[(nt * 16 + lq) * VT_LD + ((sb * 32 + g * 8 + 8 * ((nt * 16 + lq) >> 3)) & (KVB - 1))]);
-                acc_o[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, acc_o[nt], 0, 0, 0);
-            }
-        }
+        ac_wave_lds_fence();
+        f32x4 s[AC_NST];
+        ac_scores_image<NKK>(Ks, lq, g, qf, s);
+        ac_scale_o(acc_o, ac_softmax_update(s, split * DEC_CHUNK, g, sc, mask, m_run, l_run));
+        bf16x8 pf[AC_NSB];
+        ac_pack_p(s, pf);
+        ac_pv<NDT>(Vt, lq, g, pf, acc_o);
     }
-    // ---- the four partials meet in LDS (each in its wave's K image): row lq -> [DV] un-normalised O (exp2 domain), m, l
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    float* part = reinterpret_cast<float*>(Ks);
-#pragma unroll
-    for (int nt = 0; nt < NDT; ++nt) *reinterpret_cast<f32x4*>(part + lq * PLD + nt * 16 + g * 4) = acc_o[nt];
-    if (g == 0) { part[lq * PLD + DV] = m_run; part[lq * PLD + DV + 1] = l_run; }
+    // ---- the four partials meet in LDS (each in its wave's K image)
+    ac_wave_lds_fence();
+    ac_store_partial<PLD>(reinterpret_cast<float*>(Ks), lq, g, acc_o, m_run, l_run);
     __syncthreads();
     // 256 threads: row tid / 16, DV / 16 consecutive columns each
-    {
-        constexpr int CPT = DV / 16;
-        const int row = tid >> 4, c0 = (tid & 15) * CPT;
-        const int Rr = rt * 16 + row;
-        if (Rr < G * p.Lq) {
-            const float* pw[DEC_FUSED_WAVES];
-            float ms[DEC_FUSED_WAVES], m = -INFINITY;
-#pragma unroll
-            for (int w = 0; w < DEC_FUSED_WAVES; ++w) {
-                pw[w] = reinterpret_cast<const float*>(reinterpret_cast<const bf16*>(dec_smem) + w * PER_WAVE) + row * PLD;
-                ms[w] = pw[w][DV];
-                m = fmaxf(m, ms[w]);
-            }
-            const float m_use = (m == -INFINITY) ? 0.f : m;
-            float l = 0.f, o[CPT];
-#pragma unroll
-            for (int c = 0; c < CPT; ++c) o[c] = 0.f;
-#pragma unroll
-            for (int w = 0; w < DEC_FUSED_WAVES; ++w) {
-                const float wl = (ms[w] == -INFINITY) ? 0.f : exp2f(ms[w] - m_use);
-                l += pw[w][DV + 1] * wl;
-#pragma unroll
-                for (int c = 0; c < CPT; ++c) o[c] += pw[w][c0 + c] * wl;
-            }
-            const float inv = l > 0.f ? 1.0f / l : 0.f;
-            const int hd = kh * G + Rr / p.Lq, qp = Rr % p.Lq;
-            bf16* O = reinterpret_cast<bf16*>(p.O) + (size_t)b * p.o_bs + (size_t)qp * p.o_rs + (size_t)hd * p.o_hs;
-#pragma unroll
-            for (int c = 0; c < CPT; ++c)
-                if (c0 + c < p.D) O[c0 + c] = (bf16)(o[c] * inv);
-        }
-    }
+    dec_write_rows<DEC_FUSED_WAVES, PER_WAVE, DV>(p, dec_smem, tid, kh, rt, b);
 }
 
 // Round 5: the same one-launch decode attention with the key axis spread over EIGHT waves and a quarter of the LDS. The 4-wave kernel above
@@ -567,12 +405,13 @@ __global__ __launch_bounds__(DEC_FUSED_WAVES * 64) void attn_decode_fused_kernel
 //   * the next chunk's K and V are requested as soon as the current chunk's S = K Q^T MFMAs have consumed the K registers (V's registers were
 //     freed by the LDS store pass): the prefetch needs no second register set;
 //   * 8 waves x 9 KiB = 72 KiB per workgroup, two chunks per wave at Lk <= 1024.
-// The chunk arithmetic (scores, running max / sum, P V) is the 4-wave kernel's; the eight partials meet in LDS in wave order.
+// The chunk arithmetic (scores, running max / sum, P V) is the 4-wave kernel's (attention_chunk.h; the store of the two half images is this
+// kernel's own); the eight partials meet in LDS in wave order.
 constexpr int DEC8_WAVES = 8;
 
 template <int DP, int DV>
 __global__ __launch_bounds__(DEC8_WAVES * 64) void attn_decode_fused8_kernel(AttnArgs p, int nsplit, int rtiles) {
-    constexpr int KVB = 64, VT_LD = KVB + 8, VCPR = DV / 8, NKK = DP / 32, NST = KVB / 16, NSB = KVB / 32, NDT = DV / 16, HDT = NDT / 2, DH = DV / 2;
+    constexpr int KVB = AC_KVB, VT_LD = AC_VT_LD, VCPR = DV / 8, NKK = DP / 32, NDT = DV / 16, HDT = NDT / 2, DH = DV / 2;
     constexpr int PER_WAVE = DH * VT_LD;                        // bf16 elements of one wave's half V^T image
     constexpr int PLD = DV + 2;                                 // partial row: DV x O, m, l (f32)
     static_assert(16 * PLD * 4 <= PER_WAVE * 2, "the partial of a wave fits its V^T image");
@@ -655,83 +494,27 @@ __global__ __launch_bounds__(DEC8_WAVES * 64) void attn_decode_fused8_kernel(Att
         }
     }
     constexpr int NVI = KVB * VCPR / 64;
-    static_assert((KVB * VCPR) % 64 == 0, "chunk pieces must divide evenly over the wave");
-    bf16x8 kf[NST][NKK], vreg[NVI];
+    bf16x8 kf[AC_NST][NKK], vreg[NVI];
     auto fetch = [&](int kv0) {
-#pragma unroll
-        for (int t = 0; t < NST; ++t) {
-            const int kv = kv0 + t * 16 + lq;
-            const bf16* kr = K + (size_t)(kv < len_k ? kv : len_k - 1) * p.k_rs + g * 8;      // (keys beyond len_k: a valid row, their scores are masked)
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) kf[t][kk] = (kk * 32 + g * 8 < p.D) ? *reinterpret_cast<const bf16x8*>(kr + kk * 32) : zero8;
-        }
-#pragma unroll
-        for (int u = 0; u < NVI; ++u) {
-            const int q = lane + u * 64, row = q / VCPR, c = q % VCPR, kv = kv0 + row;
-            vreg[u] = (kv < len_k) ? *reinterpret_cast<const bf16x8*>(V + (size_t)kv * p.v_rs + c * 8) : zero8;
-        }
+        ac_fetch_kf<NKK, true>(K, p.k_rs, kv0, len_k, p.D, lq, g, kf);
+        ac_fetch_v<DV>(V, p.v_rs, kv0, len_k, lane, vreg);
     };
     const float sc = p.scale * 1.4426950408889634f;
-    const int causal_shift = len_k - p.Lq;
+    const auto mask = dec_mask(p, live, qpos, len_k);
     const int vc = lane % VCPR;                    // this lane's 8-dim chunk of a V row (the same for every piece u: 64 % VCPR == 0)
     int split = wave;
     if (split * DEC_CHUNK < len_k) fetch(split * DEC_CHUNK);
     for (; split * DEC_CHUNK < len_k; split += DEC8_WAVES) {
-        const int kv0 = split * DEC_CHUNK;
-        // ---- S^T = K Q^T from the register fragments
-        f32x4 s[NST];
-#pragma unroll
-        for (int t = 0; t < NST; ++t) {
-            s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t][kk], qf[kk], s[t], 0, 0, 0);
-        }
+        f32x4 s[AC_NST];
+        ac_scores(kf, qf, s);
         // V registers of this chunk are parked in a second set only logically: the two half images are written one after the other below,
         // so the registers stay live until the second store pass; the NEXT chunk's V therefore goes to the same registers only after it
         bf16x8 vcur[NVI];
 #pragma unroll
         for (int u = 0; u < NVI; ++u) vcur[u] = vreg[u];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < NST; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kv = kv0 + t * 16 + g * 4 + r;
-                const bool ok = live && (kv < len_k) && (!p.causal || kv <= qpos + causal_shift);
-                const float v = ok ? s[t][r] * sc : -INFINITY;
-                s[t][r] = v;
-                mx = fmaxf(mx, v);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-        const float alpha = (m_run == -INFINITY) ? 0.f : exp2f(m_run - m_use);
-        float rs = 0.f;
-#pragma unroll
-        for (int t = 0; t < NST; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = exp2f(s[t][r] - m_use);
-                s[t][r] = e;
-                rs += e;
-            }
-        rs += __shfl_xor(rs, 16);
-        rs += __shfl_xor(rs, 32);
-        l_run = l_run * alpha + rs;
-        m_run = m_new;
-#pragma unroll
-        for (int nt = 0; nt < NDT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc_o[nt][r] *= alpha;
-        bf16x8 pf[NSB];
-#pragma unroll
-        for (int sb = 0; sb < NSB; ++sb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                pf[sb][r] = (bf16)s[2 * sb][r];
-                pf[sb][4 + r] = (bf16)s[2 * sb + 1][r];
-            }
+        ac_scale_o(acc_o, ac_softmax_update(s, split * DEC_CHUNK, g, sc, mask, m_run, l_run));
+        bf16x8 pf[AC_NSB];
+        ac_pack_p(s, pf);
         // ---- O^T += V^T P^T, one half of the head dim at a time through the wave's half image
 #pragma unroll
         for (int hv = 0; hv < 2; ++hv) {
@@ -746,56 +529,15 @@ __global__ __launch_bounds__(DEC8_WAVES * 64) void attn_decode_fused8_kernel(Att
                 }
             }
             if (hv == 1 && (split + DEC8_WAVES) * DEC_CHUNK < len_k) fetch((split + DEC8_WAVES) * DEC_CHUNK);   // next chunk in flight under this half's math
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int sb = 0; sb < NSB; ++sb)
-#pragma unroll
-                for (int n2 = 0; n2 < HDT; ++n2) {
-                    const int dl = n2 * 16 + lq, d = hv * DH + dl;               // row of the half image / head dim
-                    const bf16x8 vf = *reinterpret_cast<const bf16x8*>(&Vt[dl * VT_LD + ((sb * 32 + g * 8 + 8 * (d >> 3)) & (KVB - 1))]);
-                    acc_o[hv * HDT + n2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[sb], acc_o[hv * HDT + n2], 0, 0, 0);
-                }
+            ac_wave_lds_fence();
+            ac_pv<HDT>(Vt, lq, g, pf, acc_o, hv * HDT);
         }
     }
-    // ---- the eight partials meet in LDS (each in its wave's image): row lq -> [DV] un-normalised O (exp2 domain), m, l
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    float* part = reinterpret_cast<float*>(Vt);
-#pragma unroll
-    for (int nt = 0; nt < NDT; ++nt) *reinterpret_cast<f32x4*>(part + lq * PLD + nt * 16 + g * 4) = acc_o[nt];
-    if (g == 0) { part[lq * PLD + DV] = m_run; part[lq * PLD + DV + 1] = l_run; }
+    // ---- the eight partials meet in LDS (each in its wave's image)
+    ac_wave_lds_fence();
+    ac_store_partial<PLD>(reinterpret_cast<float*>(Vt), lq, g, acc_o, m_run, l_run);
     __syncthreads();
-    if (tid < 256) {        // 256 threads: row tid / 16, DV / 16 consecutive columns each
-        constexpr int CPT = DV / 16;
-        const int row = tid >> 4, c0 = (tid & 15) * CPT;
-        const int Rr = rt * 16 + row;
-        if (Rr < G * p.Lq) {
-            float m = -INFINITY;
-#pragma unroll
-            for (int w = 0; w < DEC8_WAVES; ++w)
-                m = fmaxf(m, (reinterpret_cast<const float*>(reinterpret_cast<const bf16*>(dec_smem) + w * PER_WAVE) + row * PLD)[DV]);
-            const float m_use = (m == -INFINITY) ? 0.f : m;
-            float l = 0.f, o[CPT];
-#pragma unroll
-            for (int c = 0; c < CPT; ++c) o[c] = 0.f;
-#pragma unroll
-            for (int w = 0; w < DEC8_WAVES; ++w) {
-                const float* pw = reinterpret_cast<const float*>(reinterpret_cast<const bf16*>(dec_smem) + w * PER_WAVE) + row * PLD;
-                const float ms = pw[DV];
-                const float wl = (ms == -INFINITY) ? 0.f : exp2f(ms - m_use);
-                l += pw[DV + 1] * wl;
-#pragma unroll
-                for (int c = 0; c < CPT; ++c) o[c] += pw[c0 + c] * wl;
-            }
-            const float inv = l > 0.f ? 1.0f / l : 0.f;
-            const int hd = kh * G + Rr / p.Lq, qp = Rr % p.Lq;
-            bf16* O = reinterpret_cast<bf16*>(p.O) + (size_t)b * p.o_bs + (size_t)qp * p.o_rs + (size_t)hd * p.o_hs;
-#pragma unroll
-            for (int c = 0; c < CPT; ++c)
-                if (c0 + c < p.D) O[c0 + c] = (bf16)(o[c] * inv);
-        }
-    }
+    if (tid < 256) dec_write_rows<DEC8_WAVES, PER_WAVE, DV>(p, dec_smem, tid, kh, rt, b);
 }
 
 template <int DP, int DV>
@@ -813,28 +555,12 @@ int launch_decode(const AttnArgs& p, hipStream_t stream) {
                                         ((uintptr_t)p.k_new % 16) == 0 && ((uintptr_t)p.v_new % 16) == 0 && p.k_rs % 8 == 0 && p.v_rs % 8 == 0),
                         "attention(rope): needs rope_sin, k_new, v_new, d = 128, causal decode and 16-byte aligned rows");
             constexpr size_t LDS8 = (size_t)DEC8_WAVES * (DV / 2) * (64 + 8) * sizeof(bf16);
-            auto kern8 = attn_decode_fused8_kernel<DP, DV>;
-            static bool attr8_done = false;
-            if (!attr8_done) {
-                INA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS8));
-                attr8_done = true;
-            }
-            hipLaunchKernelGGL(kern8, dim3(p.Hkv * rtiles, p.B), dim3(DEC8_WAVES * 64), LDS8, stream, p, nsplit, rtiles);
-            INA_HIP_CHECK(hipGetLastError());
-            return 0;
+            return ac_launch_big_lds<attn_decode_fused8_kernel<DP, DV>>(dim3(p.Hkv * rtiles, p.B), DEC8_WAVES * 64, LDS8, stream, p, nsplit, rtiles);
         }
     }
     if (nsplit <= DEC_FUSED_MAX_CHUNKS && p.kernel != 1) {      // (ina_attn_args.kernel = 1 pins the two-launch split + combine pair: parity tests compare)
         constexpr size_t LDS = (size_t)DEC_FUSED_WAVES * (64 * (DP + 8) + DV * (64 + 8)) * sizeof(bf16);
-        auto kern = attn_decode_fused_kernel<DP, DV>;
-        static bool attr_done = false;
-        if (!attr_done) {
-            INA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-            attr_done = true;
-        }
-        hipLaunchKernelGGL(kern, dim3(p.Hkv * rtiles, p.B), dim3(DEC_FUSED_WAVES * 64), LDS, stream, p, nsplit, rtiles);
-        INA_HIP_CHECK(hipGetLastError());
-        return 0;
+        return ac_launch_big_lds<attn_decode_fused_kernel<DP, DV>>(dim3(p.Hkv * rtiles, p.B), DEC_FUSED_WAVES * 64, LDS, stream, p, nsplit, rtiles);
     }
     const size_t bytes = (size_t)p.B * p.Hkv * rtiles * nsplit * 16 * (DV + 2) * sizeof(float);
     float* ws = nullptr;

@@ -9,17 +9,12 @@
 // t*16 + (l >> 4)*4 + r of a block, so probabilities and dS never leave their lane before they are the B operand of the next MFMA:
 //   MODE 0  rows = queries:  S = Q K^T, dP = dO V^T, dS = P (dP - delta) scale, dQ += dS K      (also writes lse / delta)
 //   MODE 1  rows = keys:     S^T, dP^T the same way with the roles swapped,     dK += dS^T Q,  dV += P^T dO
-// The transposed column-side images (K^T for dQ; Q^T and dO^T for dK / dV) use the forward kernel's key permutation vt_pos.
+// The transposed column-side images (K^T for dQ; Q^T and dO^T for dK / dV) use the forward kernel's key permutation vt_pos (attention_chunk.h).
+#include "attention_chunk.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace {
-
-__device__ __forceinline__ int vt_pos(int kv_local) {
-    int sub = kv_local >> 5, w = kv_local & 31;
-    int t = w >> 4, x = w & 15;
-    return (sub << 5) + ((x >> 2) << 3) + (x & 3) + (t << 2);
-}
 
 constexpr int CB = 64;              // column-side block rows
 constexpr int T_LD = CB + 8;        // row length of a transposed image

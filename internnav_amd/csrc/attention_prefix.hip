@@ -10,27 +10,21 @@
 // Structure: the one-launch decode kernels of attention.hip. The G = H / Hkv query heads of a KV head and their m positions are the ROWS of
 // 16-row MFMA tiles (row R -> head kh * G + R / m, position R % m); one four-wave workgroup per (pair, KV head, row tile). The key axis is cut in
 // 64-key chunks: chunks 0 .. nc - 1 are the prefix, chunk nc is the (single, causal) suffix chunk; wave w walks chunks w, w + 4, ... with a running
-// (max, sum, O) in registers. K fragments come straight from global memory in MFMA operand layout, V goes through a wave-private transposed LDS
-// image (vt_pos of attention.hip), the next chunk is requested before the current one is multiplied. The four partials meet in LDS in wave
+// (max, sum, O) in registers. The chunk step is attention_chunk.h's: K fragments straight from global memory in MFMA operand layout, V through a
+// wave-private transposed LDS image, the next chunk requested before the current one is multiplied. The four partials meet in LDS in wave
 // order and the workgroup writes the normalised rows itself: no atomics, no workspace, the same bits on every launch.
 // Workgroups of the pairs that share a slot are neighbours in the grid (pair index runs faster than the KV head), so that the first of them brings
 // the prompt's K/V of that head in from HBM and the others can find it in L2 / Infinity Cache (an expectation: no counter was read).
-// Resources: 256 VGPRs + 129 AGPRs (two chunks' K fragments and V pieces live across the prefetch), no scratch -> one workgroup per CU.
+// Resources: 256 VGPRs + 128 AGPRs (two chunks' K fragments and V pieces live across the prefetch), no scratch -> one workgroup per CU.
 #include <cmath>
 
+#include "attention_chunk.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace {
 
-constexpr int PFX_WAVES = 4, PFX_CHUNK = 64, PFX_D = 128;
-
-// key permutation of the V^T image (attention.hip, vt_pos): MFMA k index g*8 + j <-> key (j < 4 ? g*4 + j : 16 + g*4 + (j - 4)) per 32-key sub-block
-__device__ __forceinline__ int pfx_vt_pos(int kv_local) {
-    int sub = kv_local >> 5, w = kv_local & 31;
-    int t = w >> 4, x = w & 15;
-    return (sub << 5) + ((x >> 2) << 3) + (x & 3) + (t << 2);
-}
+constexpr int PFX_WAVES = 4, PFX_CHUNK = AC_KVB, PFX_D = 128;
 
 struct PrefixArgs {
     const bf16* Q; bf16* O;
@@ -42,8 +36,8 @@ struct PrefixArgs {
 };
 
 __global__ __launch_bounds__(PFX_WAVES * 64) void attn_prefix_kernel(PrefixArgs a) {
-    constexpr int D = PFX_D, KVB = PFX_CHUNK, VT_LD = KVB + 8, VCPR = D / 8, NKK = D / 32, NST = KVB / 16, NSB = KVB / 32, NDT = D / 16;
-    constexpr int PER_WAVE = D * VT_LD;                       // bf16 elements of one wave's V^T image
+    constexpr int D = PFX_D, KVB = PFX_CHUNK, NKK = D / 32, NDT = D / 16;
+    constexpr int PER_WAVE = D * AC_VT_LD;                       // bf16 elements of one wave's V^T image
     constexpr int PLD = D + 4;                                // partial row: D x O, m, l (f32), padded to a 16-byte pitch (f32x4 stores)
     constexpr int CPT = D / 16;                               // output columns per thread in the combine
     static_assert(16 * PLD * 4 <= PER_WAVE * 2, "the partial of a wave fits its V^T image");
@@ -94,9 +88,7 @@ __global__ __launch_bounds__(PFX_WAVES * 64) void attn_prefix_kernel(PrefixArgs 
     for (int kk = 0; kk < NKK; ++kk) qf[kk] = active ? *reinterpret_cast<const bf16x8*>(Q + kk * 32 + g * 8) : zero8;
 
     const int nc = (pfx + KVB - 1) / KVB;                      // prefix chunks; chunk nc is the suffix
-    constexpr int NVI = KVB * VCPR / 64;
-    static_assert((KVB * VCPR) % 64 == 0, "chunk pieces must divide evenly over the wave");
-    bf16x8 kf[NST][NKK], vreg[NVI];
+    bf16x8 kf[AC_NST][NKK], vreg[KVB * (D / 8) / 64];
     // chunk c of this pair: (K base, V base, row stride, first key, keys of the source) - wave uniform
     auto fetch = [&](int c) {
         const bool sfx = c == nc;
@@ -104,18 +96,8 @@ __global__ __launch_bounds__(PFX_WAVES * 64) void attn_prefix_kernel(PrefixArgs 
         const bf16* Vb = sfx ? Vs : Vc;
         const long rs = sfx ? a.s_rs : a.c_rs;
         const int kv0 = sfx ? 0 : c * KVB, len = sfx ? suf : pfx;
-#pragma unroll
-        for (int t = 0; t < NST; ++t) {
-            const int kv = kv0 + t * 16 + lq;
-            const bf16* kr = Kb + (size_t)(kv < len ? kv : len - 1) * rs + g * 8;      // (keys beyond len: a valid row, their scores are masked)
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) kf[t][kk] = *reinterpret_cast<const bf16x8*>(kr + kk * 32);
-        }
-#pragma unroll
-        for (int u = 0; u < NVI; ++u) {
-            const int q = lane + u * 64, row = q / VCPR, cc = q % VCPR, kv = kv0 + row;
-            vreg[u] = (kv < len) ? *reinterpret_cast<const bf16x8*>(Vb + (size_t)kv * rs + cc * 8) : zero8;
-        }
+        ac_fetch_kf<NKK, false>(Kb, rs, kv0, len, D, lq, g, kf);
+        ac_fetch_v<D>(Vb, rs, kv0, len, lane, vreg);
     };
     const float sc = a.scale * 1.4426950408889634f;            // exp2 domain
     int c = wave;
@@ -123,111 +105,31 @@ __global__ __launch_bounds__(PFX_WAVES * 64) void attn_prefix_kernel(PrefixArgs 
     for (; c <= nc; c += PFX_WAVES) {
         const bool sfx = c == nc;
         const int kv0 = sfx ? 0 : c * KVB, len = sfx ? suf : pfx;
-        // ---- S^T = K Q^T from the register fragments
-        f32x4 s[NST];
-#pragma unroll
-        for (int t = 0; t < NST; ++t) {
-            s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t][kk], qf[kk], s[t], 0, 0, 0);
-        }
-        // ---- V registers -> this wave's transposed image (the reads of the previous chunk were consumed by its MFMAs: the LDS queue of a wave is in order)
-#pragma unroll
-        for (int u = 0; u < NVI; ++u) {
-            const int q = lane + u * 64, row = q / VCPR, cc = q % VCPR;
-            const int pos = pfx_vt_pos(row);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) Vt[(cc * 8 + i) * VT_LD + ((pos + 8 * cc) & (KVB - 1))] = vreg[u][i];   // rotated rows: see vt_pos
-        }
+        f32x4 s[AC_NST];
+        ac_scores(kf, qf, s);
+        // V registers -> this wave's transposed image (the reads of the previous chunk were consumed by its MFMAs: the LDS queue of a wave is in order)
+        ac_store_vt_image<D>(Vt, lane, vreg);
         if (c + PFX_WAVES <= nc) fetch(c + PFX_WAVES);          // next chunk in flight under this one's math
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        // ---- mask + online softmax (lane owns packed row R, keys kv0 + t*16 + g*4 + r)
-        float mx = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < NST; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kv = kv0 + t * 16 + g * 4 + r;
-                const bool ok = active && kv < len && (!sfx || kv <= qpos);
-                const float v = ok ? s[t][r] * sc : -INFINITY;
-                s[t][r] = v;
-                mx = fmaxf(mx, v);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-        const float alpha = (m_run == -INFINITY) ? 0.f : exp2f(m_run - m_use);
-        float rs = 0.f;
-#pragma unroll
-        for (int t = 0; t < NST; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = exp2f(s[t][r] - m_use);
-                s[t][r] = e;
-                rs += e;
-            }
-        rs += __shfl_xor(rs, 16);
-        rs += __shfl_xor(rs, 32);
-        l_run = l_run * alpha + rs;
-        m_run = m_new;
-#pragma unroll
-        for (int nt = 0; nt < NDT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc_o[nt][r] *= alpha;
-        // ---- O^T += V^T P^T
-#pragma unroll
-        for (int sb = 0; sb < NSB; ++sb) {
-            bf16x8 pf;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                pf[r] = (bf16)s[2 * sb][r];
-                pf[4 + r] = (bf16)s[2 * sb + 1][r];
-            }
-#pragma unroll
-            for (int nt = 0; nt < NDT; ++nt) {
-                const bf16x8 vf = *reinterpret_cast<const bf16x8*>(&Vt[(nt * 16 + lq) * VT_LD + ((sb * 32 + g * 8 + 8 * ((nt * 16 + lq) >> 3)) & (KVB - 1))]);
-                acc_o[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, acc_o[nt], 0, 0, 0);
-            }
-        }
+        ac_wave_lds_fence();
+        ac_scale_o(acc_o, ac_softmax_update(s, kv0, g, sc, [&](int kv) { return active && kv < len && (!sfx || kv <= qpos); }, m_run, l_run));
+        bf16x8 pf[AC_NSB];
+        ac_pack_p(s, pf);
+        ac_pv<NDT>(Vt, lq, g, pf, acc_o);
     }
-    // ---- the four partials meet in LDS (each in its wave's image): row lq -> [D] un-normalised O (exp2 domain), m, l
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    float* part = reinterpret_cast<float*>(Vt);
-#pragma unroll
-    for (int nt = 0; nt < NDT; ++nt) *reinterpret_cast<f32x4*>(part + lq * PLD + nt * 16 + g * 4) = acc_o[nt];
-    if (g == 0) { part[lq * PLD + D] = m_run; part[lq * PLD + D + 1] = l_run; }
+    // ---- the four partials meet in LDS (each in its wave's image)
+    ac_wave_lds_fence();
+    ac_store_partial<PLD>(reinterpret_cast<float*>(Vt), lq, g, acc_o, m_run, l_run);
     __syncthreads();
-    {   // 256 threads: row tid / 16, D / 16 consecutive columns each; the waves' partials are summed in wave order
+    {   // 256 threads: row tid / 16, D / 16 consecutive columns each
         const int row = tid >> 4, c0 = (tid & 15) * CPT;
         const int Rr = rt * 16 + row;
         if (Rr < G * a.m) {
-            const float* pw[PFX_WAVES];
-            float ms[PFX_WAVES], mm = -INFINITY;
-#pragma unroll
-            for (int w = 0; w < PFX_WAVES; ++w) {
-                pw[w] = reinterpret_cast<const float*>(reinterpret_cast<const bf16*>(pfx_smem) + w * PER_WAVE) + row * PLD;
-                ms[w] = pw[w][D];
-                mm = fmaxf(mm, ms[w]);
-            }
-            const float m_use = (mm == -INFINITY) ? 0.f : mm;
-            float l = 0.f, o[CPT];
-#pragma unroll
-            for (int cc = 0; cc < CPT; ++cc) o[cc] = 0.f;
-#pragma unroll
-            for (int w = 0; w < PFX_WAVES; ++w) {
-                const float wl = (ms[w] == -INFINITY) ? 0.f : exp2f(ms[w] - m_use);
-                l += pw[w][D + 1] * wl;
-#pragma unroll
-                for (int cc = 0; cc < CPT; ++cc) o[cc] += pw[w][c0 + cc] * wl;
-            }
-            const float inv = l > 0.f ? 1.0f / l : 0.f;        // (rows at or behind suf_len: l = 0 -> zeros)
+            float o[CPT];
+            ac_combine<PFX_WAVES, PER_WAVE, PLD, D>(pfx_smem, row, c0, o);       // (rows at or behind suf_len: l = 0 -> zeros)
             const int hd = kh * G + Rr / a.m, qp = Rr % a.m;
             bf16* op = O + (size_t)qp * a.o_rs + (size_t)hd * a.o_hs + c0;
-            const bf16x4 lo = {(bf16)(o[0] * inv), (bf16)(o[1] * inv), (bf16)(o[2] * inv), (bf16)(o[3] * inv)};
-            const bf16x4 hi = {(bf16)(o[4] * inv), (bf16)(o[5] * inv), (bf16)(o[6] * inv), (bf16)(o[7] * inv)};
+            const bf16x4 lo = {(bf16)o[0], (bf16)o[1], (bf16)o[2], (bf16)o[3]};
+            const bf16x4 hi = {(bf16)o[4], (bf16)o[5], (bf16)o[6], (bf16)o[7]};
             *reinterpret_cast<bf16x4*>(op) = lo;
             *reinterpret_cast<bf16x4*>(op + 4) = hi;
         }
@@ -268,12 +170,5 @@ int ina_launch_attention_prefix(const void* Q, long q_ps, long q_rs, long q_hs, 
     InaProfScope prof(INA_PROF_ATTN, 4.0 * P * H * (double)m * keys * D,
                       2.0 * D * ((double)P * H * m * 2.0 + 2.0 * (double)P * Hkv * ((double)max_pfx + m)), stream);
     constexpr size_t LDS = (size_t)PFX_WAVES * PFX_D * (PFX_CHUNK + 8) * sizeof(bf16);
-    static bool attr_done = false;
-    if (!attr_done) {
-        INA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_prefix_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(attn_prefix_kernel, dim3((unsigned)(P * rtiles), Hkv), dim3(PFX_WAVES * 64), LDS, stream, a);
-    INA_HIP_CHECK(hipGetLastError());
-    return 0;
+    return ac_launch_big_lds<attn_prefix_kernel>(dim3((unsigned)(P * rtiles), Hkv), PFX_WAVES * 64, LDS, stream, a);
 }

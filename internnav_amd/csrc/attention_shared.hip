@@ -14,24 +14,19 @@
 // place j the 64-key chunks of that candidate's tail; a tail chunk of place j is masked for the rows of the other places.
 // Bits do not depend on neighbours: the wave that owns a chunk is a function of the row's OWN chunk index (prefix chunk c -> wave c mod 4, tail
 // chunk t of any place -> wave (nc + t) mod 4), a wave walks its chunks in (prefix, place 0, place 1, ...) order, and a chunk that is masked
-// for a row leaves that row's running (max, sum, O) exactly as it was (alpha = 1 by construction - never exp2(-inf - -inf) -, e = 0, O += 0).
+// for a row leaves that row's running (max, sum, O) exactly as it was (alpha = 1 by construction - never exp2(-inf - -inf) -, e = 0, O += 0:
+// the UNIT_ALPHA form of ac_softmax_update, attention_chunk.h, which holds the chunk step of this kernel).
 // So every wave sees, per row, the row's own chunks in the row's own order whatever else shares the tile. The four partials meet in LDS in wave
 // order and the workgroup writes the normalised rows itself: no atomics, no workspace, the same bits on every launch.
 #include <cmath>
 
+#include "attention_chunk.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace {
 
-constexpr int SHR_WAVES = 4, SHR_CHUNK = 64, SHR_D = 128;
-
-// key permutation of the V^T image (attention.hip, vt_pos)
-__device__ __forceinline__ int shr_vt_pos(int kv_local) {
-    int sub = kv_local >> 5, w = kv_local & 31;
-    int t = w >> 4, x = w & 15;
-    return (sub << 5) + ((x >> 2) << 3) + (x & 3) + (t << 2);
-}
+constexpr int SHR_WAVES = 4, SHR_CHUNK = AC_KVB, SHR_D = 128;
 
 struct SharedArgs {
     const bf16* Q; bf16* O;
@@ -43,8 +38,8 @@ struct SharedArgs {
 };
 
 __global__ __launch_bounds__(SHR_WAVES * 64) void attn_shared_kernel(SharedArgs a) {
-    constexpr int D = SHR_D, KVB = SHR_CHUNK, VT_LD = KVB + 8, VCPR = D / 8, NKK = D / 32, NST = KVB / 16, NSB = KVB / 32, NDT = D / 16;
-    constexpr int PER_WAVE = D * VT_LD;                       // bf16 elements of one wave's V^T image
+    constexpr int D = SHR_D, KVB = SHR_CHUNK, NKK = D / 32, NDT = D / 16;
+    constexpr int PER_WAVE = D * AC_VT_LD;                       // bf16 elements of one wave's V^T image
     constexpr int PLD = D + 4;                                // partial row: D x O, m, l (f32), padded to a 16-byte pitch
     constexpr int CPT = D / 16;                               // output columns per thread in the combine
     static_assert(16 * PLD * 4 <= PER_WAVE * 2, "the partial of a wave fits its V^T image");
@@ -113,9 +108,7 @@ __global__ __launch_bounds__(SHR_WAVES * 64) void attn_shared_kernel(SharedArgs 
             c = t0;
         }
     };
-    constexpr int NVI = KVB * VCPR / 64;
-    static_assert((KVB * VCPR) % 64 == 0, "chunk pieces must divide evenly over the wave");
-    bf16x8 kf[NST][NKK], vreg[NVI];
+    bf16x8 kf[AC_NST][NKK], vreg[KVB * (D / 8) / 64];
     auto fetch = [&](int j, int c) {
         const bool tail = j >= 0;
         const size_t toff = tail ? (size_t)s_row[j] * a.t_ps + (size_t)kh * a.t_hs : 0;
@@ -123,18 +116,8 @@ __global__ __launch_bounds__(SHR_WAVES * 64) void attn_shared_kernel(SharedArgs 
         const bf16* Vb = tail ? a.Vt + toff : Vc;
         const long rs = tail ? a.t_rs : a.c_rs;
         const int kv0 = c * KVB, len = tail ? s_tl[j] : pfx;
-#pragma unroll
-        for (int t = 0; t < NST; ++t) {
-            const int kv = kv0 + t * 16 + lq;
-            const bf16* kr = Kb + (size_t)(kv < len ? kv : len - 1) * rs + g * 8;      // (keys beyond len: a valid row, their scores are masked)
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) kf[t][kk] = *reinterpret_cast<const bf16x8*>(kr + kk * 32);
-        }
-#pragma unroll
-        for (int u = 0; u < NVI; ++u) {
-            const int q = lane + u * 64, row = q / VCPR, cc = q % VCPR, kv = kv0 + row;
-            vreg[u] = (kv < len) ? *reinterpret_cast<const bf16x8*>(Vb + (size_t)kv * rs + cc * 8) : zero8;
-        }
+        ac_fetch_kf<NKK, false>(Kb, rs, kv0, len, D, lq, g, kf);
+        ac_fetch_v<D>(Vb, rs, kv0, len, lane, vreg);
     };
     const float sc = a.scale * 1.4426950408889634f;            // exp2 domain
     int j = -1, c = wave - SHR_WAVES;
@@ -143,114 +126,33 @@ __global__ __launch_bounds__(SHR_WAVES * 64) void attn_shared_kernel(SharedArgs 
     while (j < cpt) {
         const int kv0 = c * KVB, len = j < 0 ? pfx : s_tl[j];
         const bool mine = active && (j < 0 || j == place);     // a tail chunk of another place: masked for this row
-        // ---- S^T = K Q^T from the register fragments
-        f32x4 s[NST];
-#pragma unroll
-        for (int t = 0; t < NST; ++t) {
-            s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t][kk], qf[kk], s[t], 0, 0, 0);
-        }
-        // ---- V registers -> this wave's transposed image
-#pragma unroll
-        for (int u = 0; u < NVI; ++u) {
-            const int q = lane + u * 64, row = q / VCPR, cc = q % VCPR;
-            const int pos = shr_vt_pos(row);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) Vt[(cc * 8 + i) * VT_LD + ((pos + 8 * cc) & (KVB - 1))] = vreg[u][i];   // rotated rows: see vt_pos
-        }
+        f32x4 s[AC_NST];
+        ac_scores(kf, qf, s);
+        ac_store_vt_image<D>(Vt, lane, vreg);
         int jn = j, cn = c;
         advance(jn, cn);
         if (jn < cpt) fetch(jn, cn);                           // next chunk in flight under this one's math
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        // ---- mask + online softmax (lane owns packed row lq, keys kv0 + t*16 + g*4 + r)
-        float mx = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < NST; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kv = kv0 + t * 16 + g * 4 + r;
-                const float v = (mine && kv < len) ? s[t][r] * sc : -INFINITY;
-                s[t][r] = v;
-                mx = fmaxf(mx, v);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-        // an unchanged maximum (every masked chunk) scales by exactly 1, a first chunk by 0: exp2 never sees -inf - -inf
-        const float alpha = (m_new == m_run) ? 1.f : (m_run == -INFINITY) ? 0.f : exp2f(m_run - m_use);
-        float rs = 0.f;
-#pragma unroll
-        for (int t = 0; t < NST; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = exp2f(s[t][r] - m_use);
-                s[t][r] = e;
-                rs += e;
-            }
-        rs += __shfl_xor(rs, 16);
-        rs += __shfl_xor(rs, 32);
-        l_run = l_run * alpha + rs;
-        m_run = m_new;
-#pragma unroll
-        for (int nt = 0; nt < NDT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc_o[nt][r] *= alpha;
-        // ---- O^T += V^T P^T
-#pragma unroll
-        for (int sb = 0; sb < NSB; ++sb) {
-            bf16x8 pf;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                pf[r] = (bf16)s[2 * sb][r];
-                pf[4 + r] = (bf16)s[2 * sb + 1][r];
-            }
-#pragma unroll
-            for (int nt = 0; nt < NDT; ++nt) {
-                const bf16x8 vf = *reinterpret_cast<const bf16x8*>(&Vt[(nt * 16 + lq) * VT_LD + ((sb * 32 + g * 8 + 8 * ((nt * 16 + lq) >> 3)) & (KVB - 1))]);
-                acc_o[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, acc_o[nt], 0, 0, 0);
-            }
-        }
+        ac_wave_lds_fence();
+        ac_scale_o(acc_o, ac_softmax_update<true>(s, kv0, g, sc, [&](int kv) { return mine && kv < len; }, m_run, l_run));
+        bf16x8 pf[AC_NSB];
+        ac_pack_p(s, pf);
+        ac_pv<NDT>(Vt, lq, g, pf, acc_o);
         j = jn;
         c = cn;
     }
-    // ---- the four partials meet in LDS (each in its wave's image): row lq -> [D] un-normalised O (exp2 domain), m, l
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    float* part = reinterpret_cast<float*>(Vt);
-#pragma unroll
-    for (int nt = 0; nt < NDT; ++nt) *reinterpret_cast<f32x4*>(part + lq * PLD + nt * 16 + g * 4) = acc_o[nt];
-    if (g == 0) { part[lq * PLD + D] = m_run; part[lq * PLD + D + 1] = l_run; }
+    // ---- the four partials meet in LDS (each in its wave's image)
+    ac_wave_lds_fence();
+    ac_store_partial<PLD>(reinterpret_cast<float*>(Vt), lq, g, acc_o, m_run, l_run);
     __syncthreads();
-    {   // 256 threads: packed row tid / 16, D / 16 consecutive columns each; the waves' partials are summed in wave order
+    {   // 256 threads: packed row tid / 16, D / 16 consecutive columns each
         const int row = tid >> 4, c0 = (tid & 15) * CPT;
         const int pl = row / G;
         if (pl < cpt && s_row[pl] >= 0) {
-            const float* pw[SHR_WAVES];
-            float ms[SHR_WAVES], mm = -INFINITY;
-#pragma unroll
-            for (int w = 0; w < SHR_WAVES; ++w) {
-                pw[w] = reinterpret_cast<const float*>(reinterpret_cast<const bf16*>(shr_smem) + w * PER_WAVE) + row * PLD;
-                ms[w] = pw[w][D];
-                mm = fmaxf(mm, ms[w]);
-            }
-            const float m_use = (mm == -INFINITY) ? 0.f : mm;
-            float l = 0.f, o[CPT];
-#pragma unroll
-            for (int cc = 0; cc < CPT; ++cc) o[cc] = 0.f;
-#pragma unroll
-            for (int w = 0; w < SHR_WAVES; ++w) {
-                const float wl = (ms[w] == -INFINITY) ? 0.f : exp2f(ms[w] - m_use);
-                l += pw[w][D + 1] * wl;
-#pragma unroll
-                for (int cc = 0; cc < CPT; ++cc) o[cc] += pw[w][c0 + cc] * wl;
-            }
-            const float inv = l > 0.f ? 1.0f / l : 0.f;        // (rows without a tail: l = 0 -> zeros)
+            float o[CPT];
+            ac_combine<SHR_WAVES, PER_WAVE, PLD, D>(shr_smem, row, c0, o);       // (rows without a tail: l = 0 -> zeros)
             bf16* op = a.O + (size_t)s_row[pl] * a.o_rs + (size_t)(kh * G + row % G) * a.o_hs + c0;
-            const bf16x4 lo = {(bf16)(o[0] * inv), (bf16)(o[1] * inv), (bf16)(o[2] * inv), (bf16)(o[3] * inv)};
-            const bf16x4 hi = {(bf16)(o[4] * inv), (bf16)(o[5] * inv), (bf16)(o[6] * inv), (bf16)(o[7] * inv)};
+            const bf16x4 lo = {(bf16)o[0], (bf16)o[1], (bf16)o[2], (bf16)o[3]};
+            const bf16x4 hi = {(bf16)o[4], (bf16)o[5], (bf16)o[6], (bf16)o[7]};
             *reinterpret_cast<bf16x4*>(op) = lo;
             *reinterpret_cast<bf16x4*>(op + 4) = hi;
         }
@@ -290,12 +192,5 @@ int ina_launch_attention_shared(const void* Q, long q_rs, long q_hs, void* O, lo
     InaProfScope prof(INA_PROF_ATTN, 4.0 * n_rows * H * ((double)max_pfx + T) * D,
                       2.0 * D * ((double)n_rows * H * 2.0 + 2.0 * Hkv * ((double)n_tiles * max_pfx + (double)n_rows * T)), stream);
     constexpr size_t LDS = (size_t)SHR_WAVES * SHR_D * (SHR_CHUNK + 8) * sizeof(bf16);
-    static bool attr_done = false;
-    if (!attr_done) {
-        INA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_shared_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(attn_shared_kernel, dim3((unsigned)n_tiles, Hkv), dim3(SHR_WAVES * 64), LDS, stream, a);
-    INA_HIP_CHECK(hipGetLastError());
-    return 0;
+    return ac_launch_big_lds<attn_shared_kernel>(dim3((unsigned)n_tiles, Hkv), SHR_WAVES * 64, LDS, stream, a);
 }

@@ -22,8 +22,10 @@ With these single edits of a scratch copy of the kernels (never committed) the s
     row16    attn_fwd_kernel, `causal_shift = len_k - len_q` taken from p.Lk: the two causal row16 cases whose len_k is below Lk fail (k_len
              [65, 37, 0] and the packed causal case);
     dropout  `row = (...) * p.Lk` of the DROP build with len_k for p.Lk: the two k_len cases fail, salted and unsalted;
-    decode   `kv <= qpos + causal_shift` as `<` in the split, the 4-wave and the 8-wave kernel: every causal decode run fails on every kernel
-             (all 23, rope + append included), no non-causal one;
+    decode   `kv <= qpos + causal_shift` as `<` in `dec_mask` (attention.hip), the one mask of the split, the 4-wave and the 8-wave kernel: every
+             causal decode run fails on every kernel (all 23, rope + append included), no non-causal one, and nothing in the prefix / shared
+             suites, whose kernels hand the shared chunk step (attention_chunk.h) a mask of their own (`kv <= qpos` as `<` in
+             attn_prefix_kernel: the seven cases of tests/test_attention_prefix_gpu.py fail and nothing here);
     wide     `l_run *= alpha` of the deferred rescale removed: 34 of the 42 wide runs fail, both ramp cases among them;
     window   `ub = min(len_k - 1, ...)` one key later in the single-buffer build only: the four window runs on kernel 0 / 2 fail, kernel 1 passes.
 """
