@@ -307,6 +307,35 @@ int ina_attention_prefix(const void* Q, int64_t q_ps, int64_t q_rs, int64_t q_hs
                          const void* v_suf, int64_t s_ps, int64_t s_rs, int64_t s_hs, const int32_t* slot, const int32_t* pfx_len,
                          const int32_t* suf_len, int32_t P, int32_t m, int32_t H, int32_t Hkv, int32_t D, int32_t max_pfx, float scale, void* stream);
 
+/* ---- attention_prefix_tail: attention_prefix with one more read-only key segment between prefix and suffix, one launch (the latent queries
+ *      of a SAMPLED answer continue the state generate left behind: the prompt in its cache slot, the answer's own K/V either behind it in a
+ *      slot of its own or in its row of the shared-prefix tail buffer - no second prefill).
+ *  bf16 in / out, fp32 softmax and accumulation, strides in elements, D = 128. Q, O, k_cache, v_cache, k_suf, v_suf, slot, pfx_len, suf_len
+ *  and their strides: as for ina_attention_prefix.
+ *  k_tail, v_tail     n_tail_rows tails in the cache's row format (a layer of the engine's shared-prefix tails): key / value row t of tail r,
+ *             KV head kh at r * t_ps + t * t_rs + kh * t_hs (one set of strides for both pointers), at least max_tail rows in each;
+ *  tail_row, tail_len   device int32 [P]: the tail of pair p and how many of its rows the pair sees.
+ *  Query row i of pair p, i < suf_len[p], sees keys 0 .. min(pfx_len[p], max_pfx) - 1 of cache slot slot[p], then rows 0 ..
+ *  min(tail_len[p], max_tail) - 1 of tail tail_row[p], then suffix keys j <= i of pair p: nothing of another pair, no cache row at or behind
+ *  pfx_len[p], no tail row at or behind tail_len[p]. Two pairs may name the same slot and the same tail. tail_len[p] <= 0: tail_row[p] is
+ *  not looked at (-1 is legal) and the pair is computed as by ina_attention_prefix, bit for bit. k_tail, v_tail, tail_row and tail_len all
+ *  NULL: no tail at all, the launch IS ina_attention_prefix's (n_tail_rows, max_tail and the tail strides are ignored); some of them NULL
+ *  is refused.
+ *  Output rows i >= suf_len[p] are written as zeros. A slot[p] outside [0, n_slots), or a tail_row[p] outside [0, n_tail_rows) with
+ *  tail_len[p] > 0, yields NaN in the rows i < suf_len[p] of that pair and never an out-of-bounds access. Nothing is written to the cache or
+ *  the tails. The key axis is cut in 64-key chunks per segment (prefix, tail, suffix); their order and owners depend on the pair alone, so
+ *  the bits of a pair do not depend on its neighbours, and a pair with pfx_len % 64 = 0 has the bits ina_attention_prefix gives on a slot
+ *  that holds [prefix | tail]. No atomics, no workspace: two launches give the same bits; device tables only: graph capturable.
+ *  Contract: that of ina_attention_prefix, and with a tail n_tail_rows >= 1, max_tail >= 0, tail strides multiples of 8, tail pointers
+ *  16-byte aligned; anything else is refused before any HIP call. P = 0 returns 0 and launches nothing.
+ *  Plain arguments: no struct, no ABI bump. */
+int ina_attention_prefix_tail(const void* Q, int64_t q_ps, int64_t q_rs, int64_t q_hs, void* O, int64_t o_ps, int64_t o_rs, int64_t o_hs,
+                              const void* k_cache, const void* v_cache, int64_t c_ss, int64_t c_rs, int64_t c_hs, int32_t n_slots, const void* k_tail,
+                              const void* v_tail, int64_t t_ps, int64_t t_rs, int64_t t_hs, int32_t n_tail_rows, const void* k_suf, const void* v_suf,
+                              int64_t s_ps, int64_t s_rs, int64_t s_hs, const int32_t* slot, const int32_t* pfx_len, const int32_t* tail_row,
+                              const int32_t* tail_len, const int32_t* suf_len, int32_t P, int32_t m, int32_t H, int32_t Hkv, int32_t D,
+                              int32_t max_pfx, int32_t max_tail, float scale, void* stream);
+
 /* ---- attention_shared: single-token attention of n_rows rows (one returned sequence each) whose prompts stay ONCE in the System-2 KV cache,
  *      one launch (generate(do_sample=True, num_return_sequences=K, share_prefix=True): K sampled answers per prompt, no cache slot per answer).
  *  bf16 in / out, fp32 softmax and accumulation, strides in elements, D = 128, G = H / Hkv <= 16.

@@ -196,6 +196,18 @@ int ina_attention_prefix(const void* Q, int64_t q_ps, int64_t q_rs, int64_t q_hs
                                        H, Hkv, D, max_pfx, scale, reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_attention_prefix_tail(const void* Q, int64_t q_ps, int64_t q_rs, int64_t q_hs, void* O, int64_t o_ps, int64_t o_rs, int64_t o_hs,
+                              const void* k_cache, const void* v_cache, int64_t c_ss, int64_t c_rs, int64_t c_hs, int32_t n_slots, const void* k_tail,
+                              const void* v_tail, int64_t t_ps, int64_t t_rs, int64_t t_hs, int32_t n_tail_rows, const void* k_suf, const void* v_suf,
+                              int64_t s_ps, int64_t s_rs, int64_t s_hs, const int32_t* slot, const int32_t* pfx_len, const int32_t* tail_row,
+                              const int32_t* tail_len, const int32_t* suf_len, int32_t P, int32_t m, int32_t H, int32_t Hkv, int32_t D,
+                              int32_t max_pfx, int32_t max_tail, float scale, void* stream) {
+    return ina_launch_attention_prefix_tail(Q, (long)q_ps, (long)q_rs, (long)q_hs, O, (long)o_ps, (long)o_rs, (long)o_hs, k_cache, v_cache, (long)c_ss,
+                                            (long)c_rs, (long)c_hs, n_slots, k_tail, v_tail, (long)t_ps, (long)t_rs, (long)t_hs, n_tail_rows, k_suf,
+                                            v_suf, (long)s_ps, (long)s_rs, (long)s_hs, slot, pfx_len, tail_row, tail_len, suf_len, P, m, H, Hkv, D,
+                                            max_pfx, max_tail, scale, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_attention_shared(const void* Q, int64_t q_rs, int64_t q_hs, void* O, int64_t o_rs, int64_t o_hs, const void* k_cache, const void* v_cache,
                          int64_t c_ss, int64_t c_rs, int64_t c_hs, int32_t n_slots, const void* k_tail, const void* v_tail, int64_t t_ps, int64_t t_rs,
                          int64_t t_hs, int32_t T, const int32_t* tile_rows, const int32_t* tile_slot, const int32_t* tile_pfx, const int32_t* tail_len,

@@ -1,7 +1,8 @@
 // The 64-key chunk step of the single-token attention family for gfx950, defined once: attn_decode_split_kernel, attn_decode_fused_kernel and
-// attn_decode_fused8_kernel (attention.hip), attn_prefix_kernel (attention_prefix.hip) and attn_shared_kernel (attention_shared.hip).
+// attn_decode_fused8_kernel (attention.hip), attn_prefix_kernel and its twin with a tail segment, attn_prefix_tail_kernel (one body,
+// attention_prefix.hip), and attn_shared_kernel (attention_shared.hip).
 //
-// All five put 16 packed query rows in one MFMA tile and cut their key axis into chunks of AC_KVB = 64 keys. Both MFMAs are issued in the
+// All of them put 16 packed query rows in one MFMA tile and cut their key axis into chunks of AC_KVB = 64 keys. Both MFMAs are issued in the
 // "swapped" form of attention.hip: lane l owns query row lq = l & 15, lane group g = l >> 4 owns the keys t * 16 + g * 4 + r of a chunk:
 //   S^T[kv][q] = K . Q^T    -> lane holds S[q][kv0 + t * 16 + g * 4 + r] in s[t][r]
 //   O^T[d][q]  = V^T . P^T  -> lane holds O[q][nt * 16 + g * 4 + r] in acc_o[nt][r]

@@ -70,6 +70,12 @@ int ina_launch_attention_prefix(const void* Q, long q_ps, long q_rs, long q_hs, 
                                 const void* Vc, long c_ss, long c_rs, long c_hs, int n_slots, const void* Ks, const void* Vs, long s_ps, long s_rs,
                                 long s_hs, const int32_t* slot, const int32_t* pfx_len, const int32_t* suf_len, int P, int m, int H, int Hkv, int D,
                                 int max_pfx, float scale, hipStream_t stream);                                               // attention_prefix.hip
+int ina_launch_attention_prefix_tail(const void* Q, long q_ps, long q_rs, long q_hs, void* O, long o_ps, long o_rs, long o_hs, const void* Kc,
+                                     const void* Vc, long c_ss, long c_rs, long c_hs, int n_slots, const void* Kt, const void* Vt, long t_ps,
+                                     long t_rs, long t_hs, int n_tail_rows, const void* Ks, const void* Vs, long s_ps, long s_rs, long s_hs,
+                                     const int32_t* slot, const int32_t* pfx_len, const int32_t* tail_row, const int32_t* tail_len,
+                                     const int32_t* suf_len, int P, int m, int H, int Hkv, int D, int max_pfx, int max_tail, float scale,
+                                     hipStream_t stream);                                                                    // attention_prefix.hip
 int ina_launch_attention_shared(const void* Q, long q_rs, long q_hs, void* O, long o_rs, long o_hs, const void* Kc, const void* Vc, long c_ss,
                                 long c_rs, long c_hs, int n_slots, const void* Kt, const void* Vt, long t_ps, long t_rs, long t_hs, int T,
                                 const int32_t* tile_rows, const int32_t* tile_slot, const int32_t* tile_pfx, const int32_t* tail_len, int n_tiles,

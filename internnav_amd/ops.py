@@ -400,7 +400,60 @@ def attention_prefix(q: torch.Tensor, k_suf: torch.Tensor, v_suf: torch.Tensor, 
     return out
 
 
-ATTN_SHARED_MAX_GROUP = 16    # query heads per KV head of ops.attention_shared (one candidate's heads fill a 16-row tile at most)
+def attention_prefix_tail(q: torch.Tensor, k_suf: torch.Tensor, v_suf: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot: torch.Tensor,
+                          pfx_len: torch.Tensor, suf_len: torch.Tensor, k_tail: Optional[torch.Tensor] = None, v_tail: Optional[torch.Tensor] = None,
+                          tail_row: Optional[torch.Tensor] = None, tail_len: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                          scale: Optional[float] = None, max_pfx: Optional[int] = None, max_tail: Optional[int] = None) -> torch.Tensor:
+    """`attention_prefix` with one more read-only key segment between prefix and suffix (ina_attention_prefix_tail): query row i of pair p
+    (i < suf_len[p]) sees rows [0, pfx_len[p]) of cache slot slot[p], then rows [0, tail_len[p]) of tail tail_row[p], then suffix keys j <= i of
+    pair p. Nothing is written to the cache or the tails. Arguments of `attention_prefix`, and k_tail / v_tail [n_tail_rows, T, Hkv, 128] bf16
+    (equal strides, contiguous last dim; a layer of the engine's shared-prefix tails), tail_row / tail_len int32 [P] on the device, max_tail
+    (default T): the largest tail_len (longer ones are clipped). The four tail arguments come together; without them the call is
+    `attention_prefix`. tail_len <= 0 ignores tail_row; a tail row outside the buffer with tail_len > 0 gives NaN rows, as a bad slot does."""
+    assert q.dtype == k_suf.dtype == v_suf.dtype == k_cache.dtype == v_cache.dtype == torch.bfloat16
+    assert q.dim() == 4 and k_suf.dim() == 4 and k_cache.dim() == 4
+    P, m, H, D = q.shape
+    Hkv = k_suf.shape[2]
+    n_slots, S = k_cache.shape[0], k_cache.shape[1]
+    assert D == 128, f"attention_prefix_tail: head dim {D} (128 only)"
+    assert 1 <= m <= ATTN_PREFIX_MAX_ROWS, f"attention_prefix_tail: {m} suffix rows per pair (1 .. {ATTN_PREFIX_MAX_ROWS})"
+    assert Hkv > 0 and H % Hkv == 0, f"attention_prefix_tail: {H} heads over {Hkv} KV heads"
+    assert k_suf.shape == (P, m, Hkv, D) and v_suf.shape == k_suf.shape and k_suf.stride() == v_suf.stride()
+    assert k_cache.shape == (n_slots, S, Hkv, D) and v_cache.shape == k_cache.shape and k_cache.stride() == v_cache.stride() and n_slots >= 1
+    if out is None:
+        out = torch.empty(P, m, H, D, dtype=torch.bfloat16, device=q.device)
+    assert out.shape == q.shape and out.dtype == torch.bfloat16
+    assert all(t.stride(-1) == 1 for t in (q, k_suf, v_suf, k_cache, v_cache, out))
+    for t in (slot, pfx_len, suf_len):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == P and t.device == q.device
+    max_pfx = S if max_pfx is None else int(max_pfx)
+    assert 0 <= max_pfx <= S, f"attention_prefix_tail: max_pfx={max_pfx} outside the cache's {S} rows per slot"
+    tail = [k_tail, v_tail, tail_row, tail_len]
+    has_tail = tail[0] is not None
+    assert all((t is not None) == has_tail for t in tail), "attention_prefix_tail: k_tail, v_tail, tail_row and tail_len come together"
+    tp = [0] * 9                                                    # k_tail, v_tail, their three strides, n_tail_rows, tail_row, tail_len, max_tail
+    if has_tail:
+        assert k_tail.dtype == v_tail.dtype == torch.bfloat16 and k_tail.dim() == 4 and k_tail.device == q.device
+        n_tail_rows, T = k_tail.shape[0], k_tail.shape[1]
+        assert n_tail_rows >= 1 and k_tail.shape == (n_tail_rows, T, Hkv, D) and v_tail.shape == k_tail.shape and k_tail.stride() == v_tail.stride()
+        assert k_tail.stride(-1) == 1
+        for t in (tail_row, tail_len):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == P and t.device == q.device
+        max_tail = T if max_tail is None else int(max_tail)
+        assert 0 <= max_tail <= T, f"attention_prefix_tail: max_tail={max_tail} outside the {T} rows of a tail"
+        tp = [k_tail.data_ptr(), v_tail.data_ptr(), k_tail.stride(0), k_tail.stride(1), k_tail.stride(2), n_tail_rows, tail_row.data_ptr(),
+              tail_len.data_ptr(), max_tail]
+    rc = _lib.lib().ina_attention_prefix_tail(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), out.data_ptr(), out.stride(0), out.stride(1),
+                                              out.stride(2), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1),
+                                              k_cache.stride(2), n_slots, tp[0] or None, tp[1] or None, tp[2], tp[3], tp[4], tp[5], k_suf.data_ptr(),
+                                              v_suf.data_ptr(), k_suf.stride(0), k_suf.stride(1), k_suf.stride(2), slot.data_ptr(), pfx_len.data_ptr(),
+                                              tp[6] or None, tp[7] or None, suf_len.data_ptr(), P, m, H, Hkv, D, max_pfx, tp[8],
+                                              float(scale) if scale is not None else float(D) ** -0.5, _stream())
+    _lib.check(rc, "attention_prefix_tail")
+    return out
+
+
+ATTN_SHARED_MAX_GROUP = 16   # query heads per KV head of ops.attention_shared (one candidate's heads fill a 16-row tile at most)
 
 
 def attention_shared_plan(prompt_of, G: int):

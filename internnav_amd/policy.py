@@ -485,8 +485,8 @@ class InternVLAN1ForCausalLM:
         sequences. num_return_sequences=K: every prompt is prefilled ONCE (its images encoded once), its K first tokens are drawn from the
         one logits row and its cache rows are replicated into K slots; `sequences` is [B * K, S + n], prompt-major like HF's
         repeat_interleave; B * K beyond the engine's max_seqs raises CapacityError before anything is launched. With K > 1 the result
-        carries past_key_values=None, export_prefix is refused (ValueError), and generate_latents on a returned row takes the
-        reference-signature re-run path (the cached state is of B * K rows). output_logprobs under sampling works on every model
+        carries past_key_values=None, export_prefix is refused (ValueError), and generate_latents on the returned B * K rows (rows= the
+        chosen ones) continues the cached state of those rows without re-running their prompts. output_logprobs under sampling works on every model
         (token_logprobs=True is not needed: the sampling path keeps its own buffer): token_logprobs = log q of each draw, the log-softmax
         of HF's processed scores (after penalty, temperature, top-k, top-p); token_margins is not defined for a draw and is NaN inside
         the answer (0.0 behind EOS, like every masked position); answer_confidences' margin of a sampled row is NaN accordingly.
@@ -496,8 +496,8 @@ class InternVLAN1ForCausalLM:
         tail. Capacity then reads B <= max_seqs and B * K <= 64 (SKINNY_GEMM_MAX_ROWS: the passes stay on the weight-streaming kernels),
         max_new_tokens <= max_decode; CapacityError before anything is launched. The tokens are not bit-equal to the fan-out path's (another
         attention kernel: an equally valid rounding). Everything else is as with K > 1 above, for every K: EOS handling, answer_lengths,
-        output_logprobs, seed= / generator=, decode_chunk, past_key_values=None in the result, export_prefix refused, generate_latents on a
-        returned row re-runs it. The prompts' cache slots hold exactly what the prefill wrote when the call returns."""
+        output_logprobs, seed= / generator=, decode_chunk, past_key_values=None in the result, export_prefix refused, generate_latents(rows=)
+        continues the chosen rows behind prompt slot + tail. The prompts' cache slots hold exactly what the prefill wrote when the call returns."""
         smp = sampling_spec(self.generation_config, do_sample, temperature, top_k, top_p, num_return_sequences, kw)
         if share_prefix and smp is None:
             raise ValueError("share_prefix=True needs do_sample=True: greedy decoding returns one sequence per prompt and has nothing to share")
@@ -531,6 +531,7 @@ class InternVLAN1ForCausalLM:
             am = attention_mask.cpu().long()
             assert bool((am[:, 1:] <= am[:, :-1]).all()), "ragged System-2 batches are right-padded (mask = 1...1 0...0)"
         pl = 0
+        self._gen = None                                       # the cache slots (and tails) are rewritten from here on: nothing older may be continued
         self.last_kv_reuse = dict(rows=0, fallbacks=0)
         if past_key_values is not None:
             assert prefix_kv is None, "past_key_values and prefix_kv are two forms of the same reuse: pass one"
@@ -583,8 +584,11 @@ class InternVLAN1ForCausalLM:
         ids_cpu = input_ids.cpu().long()
         if K > 1:                                                 # rows are prompt-major from here on: row b * K + c = prompt b, sequence c
             plens, ids_cpu = np.repeat(plens, K), ids_cpu.repeat_interleave(K, dim=0)
-        # (K > 1: the cached state is of B * K rows and a caller continues ONE returned row: generate_latents re-runs it, the reference signature)
-        self._gen = dict(state=state, tokens=toks, lens=np.asarray(lens), prompt_lens=plens) if not fanned else None
+        # what generate_latents continues: the greedy state (and the sampled one of one sequence per prompt in its own slot) through
+        # qwen.latents, which appends to the cache; a fanned state - B * K rows, or rows without a slot - through qwen.latents_behind, which
+        # writes nothing and runs only the rows it is asked for
+        self._gen = dict(state=state, tokens=toks, lens=np.asarray(lens), prompt_lens=plens, fanned=fanned,
+                         path="shared" if share_prefix else "fan" if fanned else None)
         # every row = its own prompt, then its answer, right-filled with EOS to the common width S + n
         seqs = torch.full((B * K, S + toks.shape[1]), eos, dtype=torch.long)
         for b in range(B * K):
@@ -821,11 +825,24 @@ class InternVLAN1ForCausalLM:
         generate() on its own output (the reference's only usage, internvla_n1_policy.py:191) the KV cache is reused: the queries
         are placed behind each sequence's last kept token; otherwise the full prompt is re-run.
         rows (extension for the batched agent): the batch rows whose answer was a pixel goal - only their latents are returned
-        ([len(rows), N_QUERY, 3584]); the pass itself streams the weights once whatever the number of rows."""
+        ([len(rows), N_QUERY, 3584]); the pass itself streams the weights once whatever the number of rows.
+        After a SAMPLED generate() with num_return_sequences > 1 or share_prefix=True (output_ids = its B * K prompt-major rows, rows indexes
+        them, None = all) the state that call left is continued too, and ONLY the requested rows run: 1 + N_QUERY rows each behind the prompt
+        in its cache slot and the row's own answer K/V (its slot on the fan-out path, its tail on the shared-prefix path), read in place
+        (`QwenVLEngine.latents_behind`, ops.attention_prefix_tail) - no ViT, no prefill, nothing written, so the call can be repeated and
+        made for other rows. The requested rows' answers must equal the tokens generate() returned (up to the common width); anything
+        else - other tokens, another row count, a score_answers() call in between - takes the re-run path, as before."""
+        g = getattr(self, "_gen", None)
+        if g is not None and g.get("fanned") and output_ids.shape[0] == g["tokens"].shape[0]:
+            pl, lens, toks = g["prompt_lens"], g["lens"], g["tokens"]
+            sel = list(range(toks.shape[0])) if rows is None else [int(r) for r in rows]
+            oc = output_ids.cpu().long()
+            nt = toks.shape[1]
+            if sel and all(0 <= r < toks.shape[0] and int(pl[r]) + nt <= oc.shape[1] and torch.equal(oc[r, int(pl[r]):int(pl[r]) + nt], toks[r]) for r in sel):
+                return self.qwen.latents_behind(g["state"], sel, [int(toks[r, lens[r] - 1]) for r in sel], [int(pl[r] + lens[r] - 1) for r in sel])
         if rows is not None:
             return self.generate_latents(output_ids, pixel_values, image_grid_thw, cached_image_embeds)[torch.as_tensor(list(rows), dtype=torch.long, device=self.device)]
-        g = getattr(self, "_gen", None)
-        if g is not None and output_ids.shape[0] == g["tokens"].shape[0]:
+        if g is not None and not g.get("fanned") and output_ids.shape[0] == g["tokens"].shape[0]:
             pl, lens, toks = g["prompt_lens"], g["lens"], g["tokens"]
             oc = output_ids.cpu().long()
             nt = toks.shape[1]
@@ -833,6 +850,7 @@ class InternVLAN1ForCausalLM:
                 last = torch.stack([toks[b, lens[b] - 1] for b in range(toks.shape[0])]).to(self.device, torch.int32).view(-1, 1)
                 return self.qwen.latents(g["state"], last.contiguous(), seq_lens=pl + lens - 1)
         pv = pixel_values.to(self.device, torch.bfloat16) if pixel_values is not None and pixel_values.numel() else None
+        self._gen = None                                       # the re-run rewrites the cache slots: what generate() left is gone
         return self.qwen.generate_latents(output_ids, pv, image_grid_thw, cached_embeds=cached_image_embeds)
 
     # ---- System 1

@@ -646,8 +646,15 @@ class QwenVLEngine:
             if pfx is not None:
                 ops.rope(qkv, cos, sin, heads=nh + nkv, D=hd, col0=0, rows=rows)      # q and k in place: no cache append
                 kvc = L["kv"].view(self.B_max, Smax, 2, nkv, hd)
-                ops.attention_prefix(q4, k4, v4, kvc[:, :, 0], kvc[:, :, 1], pfx["slot"], pfx["pfx_len"], pfx["suf_len"],
-                                     out=att.view(B, S, nh, hd), max_pfx=pfx["max_pfx"])
+                tl = pfx.get("tail")
+                if tl is None:
+                    ops.attention_prefix(q4, k4, v4, kvc[:, :, 0], kvc[:, :, 1], pfx["slot"], pfx["pfx_len"], pfx["suf_len"],
+                                         out=att.view(B, S, nh, hd), max_pfx=pfx["max_pfx"])
+                else:                                                 # the pairs' own answer K/V: rows of the shared-prompt tails, read in place
+                    t5 = tl["tails"][li][: tl["rows"] * tl["T"]].view(tl["rows"], tl["T"], 2, nkv, hd)
+                    ops.attention_prefix_tail(q4, k4, v4, kvc[:, :, 0], kvc[:, :, 1], pfx["slot"], pfx["pfx_len"], pfx["suf_len"], t5[:, :, 0],
+                                              t5[:, :, 1], tl["tail_row"], tl["tail_len"], out=att.view(B, S, nh, hd), max_pfx=pfx["max_pfx"],
+                                              max_tail=tl["max_tail"])
             elif shr is not None:
                 tail = shr["tails"][li]
                 ops.rope(qkv, cos, sin, heads=nh + nkv, D=hd, col0=0, rows=rows, kv_out=tail, kv_dst=shr["kv_dst"], kv_head0=nh, v_heads=nkv)
@@ -672,10 +679,11 @@ class QwenVLEngine:
             if self.tap is not None:
                 self.tap("llm", li, x)
 
-    def _suffix_phase(self, slot, next_pos, pfx_len, suf_len, m: int) -> dict:
-        """host side of a suffix pass (`suffix_pass`): P pairs x m tokens; pair p continues the prompt in cache slot slot[p] (pfx_len[p] cached
-        tokens, next text position next_pos[p]) with suf_len[p] <= m tokens of its own. Positions are next_pos + i on all three m-rope axes -
-        what a decode would give the same tokens."""
+    def _suffix_phase(self, slot, next_pos, pfx_len, suf_len, m: int, tail_row=None, tail_len=None) -> dict:
+        """host side of a suffix pass (`suffix_pass`, `latents_behind`): P pairs x m tokens; pair p continues the prompt in cache slot slot[p]
+        (pfx_len[p] cached tokens, next text position next_pos[p]) with suf_len[p] <= m tokens of its own. Positions are next_pos + i on all
+        three m-rope axes - what a decode would give the same tokens. tail_row / tail_len (together, optional): between its slot's rows and
+        its own tokens pair p also sees the first tail_len[p] rows of row tail_row[p] of the shared-prompt tails (ops.attention_prefix_tail)."""
         dev = self.device
         slot, pfx_len, suf_len = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (slot, pfx_len, suf_len))
         P = slot.size
@@ -688,8 +696,14 @@ class QwenVLEngine:
         assert int(suf_len.min()) >= 0 and int(suf_len.max()) <= m
         pos = (np.asarray(next_pos, dtype=np.int64).reshape(-1, 1) + np.arange(m)[None]).reshape(1, P * m)
         i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(dev)
-        return dict(B=P, S=m, pos=i32(np.broadcast_to(pos, (3, P * m))), b0=0, r0=0,
-                    prefix=dict(slot=i32(slot), pfx_len=i32(pfx_len), suf_len=i32(suf_len), max_pfx=int(pfx_len.max())))
+        prefix = dict(slot=i32(slot), pfx_len=i32(pfx_len), suf_len=i32(suf_len), max_pfx=int(pfx_len.max()))
+        if tail_row is not None:
+            bufs = self._shared
+            tail_row, tail_len = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (tail_row, tail_len))
+            assert bufs is not None and tail_row.size == P and tail_len.size == P
+            assert int(tail_row.min()) >= 0 and int(tail_row.max()) < bufs.rows and int(tail_len.min()) >= 0 and int(tail_len.max()) <= bufs.T
+            prefix["tail"] = dict(tails=bufs.tails, rows=bufs.rows, T=bufs.T, tail_row=i32(tail_row), tail_len=i32(tail_len), max_tail=int(tail_len.max()))
+        return dict(B=P, S=m, pos=i32(np.broadcast_to(pos, (3, P * m))), b0=0, r0=0, prefix=prefix)
 
     def suffix_pass(self, state: dict, prompt_of, tokens, suf_len) -> torch.Tensor:
         """teacher-forced continuation of prefilled prompts WITHOUT touching their cache slots: pair p runs tokens[p, :suf_len[p]] (int [P, m],
@@ -1342,6 +1356,43 @@ class QwenVLEngine:
         self._layers(ph)
         out = torch.empty(B, nq, H, dtype=torch.bfloat16, device=self.device)
         ops.norm(self.x[:rows], self.norm_w, None, eps=1e-6, rms=True, out=out.view(B * nq, H), rows=B * nq, in_map=(nq, m + nq, m))
+        return out
+
+    def latents_behind(self, state: dict, rows, last_tokens, keep_len) -> torch.Tensor:
+        """N_QUERY latent trajectory queries behind SELECTED rows of a sampling state (`prefill(sampling=)` + `decode`), without re-running
+        their prompts and without writing anything the state lives in: no cache row, no tail row, no seen set - the call can be repeated, and
+        run again for other rows. rows int [P] (rows of the state, prompt-major; a row may be named twice); keep_len int [P]: the cached tokens
+        of each row to keep = its prompt + the kept answer tokens but the last; last_tokens int [P]: that last kept answer token, whose K/V
+        need not be cached (the last draw's are not). Pair p runs 1 + N_QUERY rows - the embedding of last_tokens[p], then latent_q - as a
+        suffix pass (`_suffix_phase`) at text positions next_pos[row] - (cur[row] - keep_len[p]) + i, what `latents` gives a greedy row:
+          shared-prompt state   slot = the row's prompt, pfx_len = the prompt's length, tail row = the row, tail_len = keep_len - prompt length;
+          one slot per row      slot = the row, pfx_len = keep_len, no tail (fan-out, or one returned sequence per prompt).
+        -> bf16 [P, N_QUERY, H] through the final RMSNorm. CapacityError before any launch if P * (1 + N_QUERY) exceeds the buffer rows."""
+        nq, H = self.latent_q.shape[0], self.H
+        m = 1 + nq
+        rows, keep = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (rows, keep_len))
+        last = np.asarray(last_tokens.cpu() if isinstance(last_tokens, torch.Tensor) else last_tokens, dtype=np.int64).reshape(-1)
+        P = rows.size
+        assert "sampling" in state and "cur" in state, "latents_behind continues a sampling state after its first decode"
+        assert P >= 1 and keep.size == P and last.size == P and int(rows.min()) >= 0 and int(rows.max()) < state["B"]
+        if P * m > self.x.shape[0]:
+            raise CapacityError(f"latent queries behind {P} rows x {m} tokens exceed the engine's {self.x.shape[0]} buffer rows")
+        cur = np.broadcast_to(np.asarray(state["cur"], dtype=np.int64), (state["B"],))[rows]
+        start = np.asarray(state["next_pos"], dtype=np.int64)[rows] - (cur - keep)
+        sh = state.get("shared")
+        if sh is not None:
+            pl = np.asarray(sh["pfx_len"], dtype=np.int64)[rows]
+            assert bool((keep >= pl).all()) and bool((keep - pl <= int(sh["tail_len"])).all()), "keep_len outside what the rows' tails hold"
+            ph = self._suffix_phase(np.asarray(sh["slot"])[rows], start, pl, np.full(P, m), m, tail_row=rows, tail_len=keep - pl)
+        else:
+            assert bool((keep >= 1).all()) and bool((keep <= cur).all()), "keep_len outside what the rows' cache slots hold"
+            ph = self._suffix_phase(rows, start, keep, np.full(P, m), m)
+        i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(self.device)
+        ops.gather_rows(self.embed, self.x_in, src=i32(last), dst=i32(np.arange(P) * m), rows=P)
+        self.x_in[: P * m].view(P, m, H)[:, 1:].copy_(self.latent_q.view(1, nq, H).expand(P, nq, H))
+        self._layers(ph)
+        out = torch.empty(P, nq, H, dtype=torch.bfloat16, device=self.device)
+        ops.norm(self.x[: P * m], self.norm_w, None, eps=1e-6, rms=True, out=out.view(P * nq, H), rows=P * nq, in_map=(nq, m, 1))
         return out
 
     # ------------------------------------------------------------------------------------------------ HF-style surface
