@@ -141,6 +141,25 @@ def _gate(c, inp, mut, dtype):
     return (g if mut == "gate_no_tanh" else torch.tanh(g)).view(1, 1, -1, 1)
 
 
+# ---- the bound's arithmetic (module docstring), shared with tests/attn_decode_ref.py
+def fp32_factor(n):
+    """16 u24 (sqrt(n) + 4): the project's model of an fp32 accumulation over n terms; n a number or a tensor."""
+    return 16.0 * U24 * ((torch.sqrt(n) if torch.is_tensor(n) else math.sqrt(n)) + 4.0)
+
+
+def exponent_eps(T, M, D):
+    """eps_j = f T_j + 4 u24 (|M| + 8): T the float64 sum_d |q_d| |k_jd| scale per key, M the row maximum of the allowed logits with a trailing
+    key axis of 1 (-inf for a row without a key: taken as 0), D the head dim."""
+    M = torch.where(torch.isinf(M), torch.zeros_like(M), M).abs()
+    return fp32_factor(D) * T + 4.0 * U24 * (M + 8.0)
+
+
+def bound_of(A, o, ref, ES, fK, ta=1.0):
+    """u8 (t A + |ref|)(1 + 2^-6) + t (fK (A + |o|) + E_S), and 0 where A = 0."""
+    bound = U8 * (ta * A + ref.abs()) * (1.0 + 2.0 ** -6) + ta * (fK * (A + o.abs()) + ES)
+    return torch.where(A > 0, bound, torch.zeros_like(bound))
+
+
 def reference(c, inp, mut=None, bounds=True, salt=0):
     """(ref, bound): float64 [B, Lq, H, D] (dense; `pack` gives the varlen rows); bound None with bounds=False."""
     B, Lq, Lk, H, Hkv, D = c["dims"]
@@ -163,15 +182,12 @@ def reference(c, inp, mut=None, bounds=True, salt=0):
     if not bounds:
         return ref, None
     ta = 1.0 if t is None else t.abs()
-    f, fK = 16.0 * U24 * (math.sqrt(D) + 4.0), 16.0 * U24 * (math.sqrt(Lk) + 4.0)
     A = torch.einsum("bhqk,bkhd->bqhd", Pm.abs(), vv.abs())
     T = torch.einsum("bqhd,bkhd->bhqk", q64.abs(), kk.abs()) * sc
     M = S.masked_fill(~allowed, float("-inf")).amax(-1, keepdim=True)
-    M = torch.where(torch.isinf(M), torch.zeros_like(M), M).abs()
-    eps = f * T + 4.0 * U24 * (M + 8.0)
+    eps = exponent_eps(T, M, D)
     ES = torch.einsum("bhqk,bkhd->bqhd", Pm.abs() * eps, vv.abs()) + o.abs() * (P * eps).sum(-1).permute(0, 2, 1)[..., None]
-    bound = U8 * (ta * A + ref.abs()) * (1.0 + 2.0 ** -6) + ta * (fK * (A + o.abs()) + ES)
-    return ref, torch.where(A > 0, bound, torch.zeros_like(bound))
+    return ref, bound_of(A, o, ref, ES, fp32_factor(Lk), ta)
 
 
 def emulate(c, inp, block=64, defer=None, salt=0, trace=None):
