@@ -558,6 +558,22 @@ int ina_sample_rows(const float* X, int32_t ldx, int32_t x_rows, int32_t rows, i
                     float temperature, int32_t top_k, float top_p, const float* u, const int32_t* src, int32_t* tok, float* logprob, int32_t* n_kept,
                     float* thr, void* stream);
 
+/* ---- automaton_mask_rows: constrained decoding - a deterministic automaton over token classes, consulted in front of the selection
+ *      kernels above (which all treat -inf as "mass 0, never chosen"); what HF's prefix_allowed_tokens_fn does, without a host round trip.
+ *  Tables: token_class u8 [vocab] (4-byte aligned), allow u32 [n_states, 8] (class c allowed in state s = bit c & 31 of word c >> 5 of
+ *  allow[s]), next u8 [n_states, 256]; 1 <= n_states <= 256. X f32 [rows, ldx] with n <= vocab live columns, modified IN PLACE.
+ *  Per row r:
+ *   advance  prev_tok == NULL: s = state_in[r]. Else s0 = state_in[r], t = prev_tok[r]: s = next[s0][class(t)] if s0 is in [0, n_states),
+ *            t in [0, n) and class(t) in allow[s0]; otherwise s = -1, and no table is read through the bad index. state_out[r] = s.
+ *   mask     s in [0, n_states): X[r][i] = -inf for every i < n whose class is not in allow[s]; allowed entries are not written (a NaN
+ *            there stays that NaN; X is never read). s outside that range: the row is left exactly as it is. Columns >= n are never touched.
+ *  state_in and state_out (int32 [rows]) must not overlap: a row is spread over many workgroups, each of which derives s from state_in. No
+ *  atomics: two launches on the same inputs give the same bits. The tables are read-only. rows == 0 launches nothing.
+ *  Refusals (a NULL pointer other than prev_tok, rows outside [0, 65535], n < 1, ldx < n, n > vocab, n_states outside [1, 256], a misaligned
+ *  token_class, overlapping state buffers) return non-zero before any HIP call. Plain arguments: no struct, no ABI bump. */
+int ina_automaton_mask_rows(float* X, int32_t ldx, int32_t rows, int32_t n, const uint8_t* token_class, int32_t vocab, const uint32_t* allow,
+                            const uint8_t* next, int32_t n_states, const int32_t* state_in, const int32_t* prev_tok, int32_t* state_out, void* stream);
+
 /* ---- select_traj: per env, rank the S samples by critic value; neg = the k lowest (ascending), pos = the k highest
  *      (descending); trajectories are cumsum_t(sample * scale).  reference: navdp_policy.py:317-320. */
 typedef struct ina_select_args {

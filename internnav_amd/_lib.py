@@ -318,6 +318,8 @@ SYMBOLS = {
                                    c_void_p]),
     "ina_sample_rows": (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, C.c_float, c_int32, C.c_float, c_int32, C.c_float,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ina_automaton_mask_rows": (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
     "ina_dit_attention": (C.c_int, [C.POINTER(DitAttnArgs), c_void_p]),
     "ina_resize_u8": (C.c_int, [C.POINTER(ResizeU8Args), c_void_p]),
     "ina_qwen_patchify_u8": (C.c_int, [C.POINTER(QwenPatchifyArgs), c_void_p]),

@@ -88,7 +88,8 @@ class InternVLAN1Agent:
         model_settings read: model_path, device, policy_name, infer_mode ('sync' | 'partial_async'), sys2_max_forward_step, num_history,
         resize_w/h, width/height (camera), continuous_traj, env_num (engine capacity), repetition_penalty (optional: overrides the
         checkpoint's generation_config.json), ignore_generation_config (optional), token_logprobs (optional, default False: every S2Output then
-        carries answer_logprob / answer_min_margin, the log-probability of the decoded answer and its smallest top-2 margin), device_preprocess (optional), device_actions
+        carries answer_logprob / answer_min_margin, the log-probability of the decoded answer and its smallest top-2 margin), answer_constraint
+        (optional: a constrain.TokenAutomaton every System-2 answer is decoded under, so it always parses), device_preprocess (optional), device_actions
         (optional, default False: System-1's trajectories become the step's action table in one kernel launch instead of one numpy
         traj_to_actions per env; `last_action_table` then holds the int32 [n, 4] table of the last System-1 call on the device).
         Tests / bench may pass a built `model` + `processor`, or a `policy_factory() -> InternVLAN1Net`, instead."""
@@ -109,7 +110,7 @@ class InternVLAN1Agent:
                 first = InternVLAN1Net(model, processor, num_history=ms.get("num_history", 8), resize_w=ms.get("resize_w", 384),
                                        resize_h=ms.get("resize_h", 384), continuous_traj=ms.get("continuous_traj", True),
                                        frame_preprocessor=frame_preprocessor, kv_reuse=ms.get("kv_reuse", False),
-                                       repetition_penalty=ms.get("repetition_penalty"))
+                                       repetition_penalty=ms.get("repetition_penalty"), answer_constraint=ms.get("answer_constraint"))
             else:
                 from . import get_config, get_policy
 
@@ -287,6 +288,11 @@ class InternVLAN1Agent:
                     pen = pens.pop()
                     if pen is not None:
                         gen_extra["repetition_penalty"] = float(pen)
+                    csts = {id(c): c for c in (getattr(it[0].policy, "answer_constraint", None) for it in items)}     # model_settings['answer_constraint']
+                    assert len(csts) == 1, "the envs of one System-2 batch carry different answer constraints"
+                    cst = next(iter(csts.values()))
+                    if cst is not None:
+                        gen_extra["constraint"] = cst
                     want_lp = bool(getattr(getattr(model, "qwen", None), "token_logprobs", False))     # model_settings['token_logprobs']
                     if want_lp:
                         gen_extra["output_logprobs"] = True

@@ -238,6 +238,12 @@ int ina_argmax_penalty_rows(const float* X, int32_t ldx, int32_t rows, int32_t n
     return ina_launch_argmax_penalty(X, ldx, rows, n, seen, ld_words, penalty, mark, out, reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_automaton_mask_rows(float* X, int32_t ldx, int32_t rows, int32_t n, const uint8_t* token_class, int32_t vocab, const uint32_t* allow,
+                            const uint8_t* next, int32_t n_states, const int32_t* state_in, const int32_t* prev_tok, int32_t* state_out, void* stream) {
+    return ina_launch_automaton_mask(X, ldx, rows, n, token_class, vocab, allow, next, n_states, state_in, prev_tok, state_out,
+                                     reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_logprob_rows(const float* X, int32_t ldx, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
                      const int32_t* target, int32_t* tok, float* logprob, float* margin, void* stream) {
     INA_REQUIRE(X && tok && logprob, "logprob_rows: X, tok and logprob required");

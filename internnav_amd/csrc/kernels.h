@@ -94,6 +94,8 @@ int ina_launch_logprob(const float* X, int ldx, int rows, int n, uint32_t* seen,
 int ina_launch_sample(const float* X, int ldx, int x_rows, int rows, int n, uint32_t* seen, int ld_words, float penalty, int mark, float temperature,
                       int top_k, float top_p, const float* u, const int32_t* src, int32_t* tok, float* logprob, int32_t* n_kept, float* thr,
                       hipStream_t stream);                                                                                   // decode_sample.hip
+int ina_launch_automaton_mask(float* X, int ldx, int rows, int n, const uint8_t* token_class, int vocab, const uint32_t* allow, const uint8_t* next,
+                              int n_states, const int32_t* state_in, const int32_t* prev_tok, int32_t* state_out, hipStream_t stream);   // decode_constrain.hip
 int ina_launch_head3(const Head3Args& p, hipStream_t stream);
 int ina_launch_seqpool(const SeqpoolArgs& p, hipStream_t stream);
 int ina_launch_select(const SelectArgs& p, hipStream_t stream);

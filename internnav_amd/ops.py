@@ -910,6 +910,29 @@ def sample_rows(x: torch.Tensor, u: torch.Tensor, tok: torch.Tensor, logprob: to
     return tok
 
 
+def automaton_mask_rows(x: torch.Tensor, tables, state_in: torch.Tensor, prev_tok: Optional[torch.Tensor], state_out: torch.Tensor) -> torch.Tensor:
+    """Constrained decoding in front of a selection launch: per f32 row r of x (modified IN PLACE) advance the row's automaton state -
+    s = state_in[r] without prev_tok, else next[state_in[r]][class(prev_tok[r])], or -1 when the state is outside the automaton, the token
+    outside [0, n) or not allowed - write it to state_out[r], and set x[r, i] = -inf wherever class(i) is not allowed in s. Allowed entries are
+    not written; a row whose s is outside the automaton is left as it is. tables: what TokenAutomaton.to(device) returns (token_class u8
+    [vocab >= n], allow 32-bit [S, 8], next u8 [S, 256]). state_in / state_out int32 [rows], distinct buffers; prev_tok int32 [rows] or None."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    rows, n = x.shape
+    cls, allow, nxt = tables.token_class, tables.allow, tables.next
+    assert cls.dtype == torch.uint8 and cls.is_contiguous() and nxt.dtype == torch.uint8 and nxt.is_contiguous()
+    S = nxt.numel() // 256
+    assert allow.dtype in (torch.uint32, torch.int32) and allow.is_contiguous() and allow.numel() == S * 8 and nxt.numel() == S * 256
+    for t in (state_in, prev_tok, state_out):
+        assert t is None or (t.dtype == torch.int32 and t.numel() == rows and t.is_contiguous())
+    if rows == 0:
+        return x
+    rc = _lib.lib().ina_automaton_mask_rows(x.data_ptr(), x.stride(0) if rows > 1 else max(x.stride(0), n), rows, n, cls.data_ptr(), cls.numel(),
+                                            allow.data_ptr(), nxt.data_ptr(), S, state_in.data_ptr(), prev_tok.data_ptr() if prev_tok is not None else None,
+                                            state_out.data_ptr(), _stream())
+    _lib.check(rc, "automaton_mask_rows")
+    return x
+
+
 def dit_v2t(kv2: torch.Tensor, heads: int, v2t: torch.Tensor) -> torch.Tensor:
     """condition V of a NextDiT block -> the transposed key-permuted image dit_attention consumes.
     kv2 bf16 [envs, Lz, 2, heads, 64] (K | V as produced by the fused kv projection); v2t bf16 [envs, heads, 64, 64]."""

@@ -452,7 +452,7 @@ class InternVLAN1ForCausalLM:
                  export_prefix: Optional[list] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
                  temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  num_return_sequences: Optional[int] = None, generator: Optional[torch.Generator] = None, seed: Optional[int] = None,
-                 share_prefix: bool = False, **kw):
+                 share_prefix: bool = False, constraint=None, **kw):
         """greedy decoding by default (do_sample=False is the only mode the reference uses, internvla_n1_policy.py:169-176). Decodes in chunks of
         `decode_chunk` device-side steps and stops once every sequence has emitted EOS. Sequences are right-filled with EOS.
         repetition_penalty / eos_token_id: None = the checkpoint's generation_config.json (`self.generation_config`; without that file 1.0
@@ -497,7 +497,15 @@ class InternVLAN1ForCausalLM:
         max_new_tokens <= max_decode; CapacityError before anything is launched. The tokens are not bit-equal to the fan-out path's (another
         attention kernel: an equally valid rounding). Everything else is as with K > 1 above, for every K: EOS handling, answer_lengths,
         output_logprobs, seed= / generator=, decode_chunk, past_key_values=None in the result, export_prefix refused, generate_latents(rows=)
-        continues the chosen rows behind prompt slot + tail. The prompts' cache slots hold exactly what the prefill wrote when the call returns."""
+        continues the chosen rows behind prompt slot + tail. The prompts' cache slots hold exactly what the prefill wrote when the call returns.
+        constraint (opt-in; None = every launch what it was): a constrain.TokenAutomaton over the model's vocabulary - what HF users reach
+        for prefix_allowed_tokens_fn for, as tables on the device. One short launch in front of every selection (ops.automaton_mask_rows)
+        advances each row's state by the token it just got and sets the logits of the tokens its state does not allow to -inf; greedy,
+        do_sample (num_return_sequences / share_prefix: a state per returned sequence), output_logprobs (the log-softmax over the ALLOWED
+        tokens: HF's processed scores) and past_key_values work as without it. At most 256 states and 256 token classes. An answer that
+        max_new_tokens cuts before an accepting state is returned as it is. score_answers is NOT constrained and not renormalised."""
+        if constraint is not None and getattr(constraint, "vocab", None) != self.qwen.cfg["vocab"]:
+            raise ValueError(f"constraint: an automaton over {getattr(constraint, 'vocab', None)} tokens, this model has {self.qwen.cfg['vocab']}")
         smp = sampling_spec(self.generation_config, do_sample, temperature, top_k, top_p, num_return_sequences, kw)
         if share_prefix and smp is None:
             raise ValueError("share_prefix=True needs do_sample=True: greedy decoding returns one sequence per prompt and has nothing to share")
@@ -556,7 +564,8 @@ class InternVLAN1ForCausalLM:
                 keep = [pv[off[i]:off[i + 1]] for i, s in enumerate(skip) if not s]
                 pv = torch.cat(keep, 0) if keep else None
         state = self.qwen.prefill(input_ids, pv, image_grid_thw, cached_embeds=cached_image_embeds, seq_lens=plens if attention_mask is not None else None,
-                                  prefix_len=pl, **({} if penalty == 1.0 else {"repetition_penalty": penalty}), **self._sampling_kw(smp, B, max_new_tokens, generator, seed, share_prefix))
+                                  prefix_len=pl, **({} if penalty == 1.0 else {"repetition_penalty": penalty}), **self._sampling_kw(smp, B, max_new_tokens, generator, seed, share_prefix),
+                                  **({} if constraint is None else {"constraint": constraint}))
         self._prefix_out = {}
         if export_prefix is not None:
             for b, n in enumerate(export_prefix):
@@ -635,6 +644,8 @@ class InternVLAN1ForCausalLM:
         the sums (device tensors).
         The log-softmax runs over the RAW logits: NO repetition penalty is applied (under teacher forcing the seen set would differ at every
         position; generate()'s token_logprobs are after the penalty - the two agree at penalty 1.0). Works without token_logprobs=True.
+        Nor is an answer constraint (generate(constraint=)) applied: the scores are over the whole vocabulary, not renormalised over the
+        tokens an automaton would allow, and a candidate the automaton rejects is scored like any other.
         Every (prompt, candidate) pair is one right-padded sequence of a normal prefill (images are encoded per pair: a prompt with four
         candidates runs the vision tower on its images four times), in groups of at most the engine's max_seqs pairs; the hidden rows that
         predict answer tokens are gathered, normed and run through lm_head into an fp32 [<= 256, vocab] buffer, and ops.logprob_rows reads the
@@ -959,7 +970,8 @@ class InternVLAN1Net:
 
     def __init__(self, config=None, processor=None, num_history: int = 8, resize_w: int = 384, resize_h: int = 384,
                  continuous_traj: bool = True, frame_preprocessor=None, model: Optional[InternVLAN1ForCausalLM] = None,
-                 vit_cache: bool = False, prefix_cache: bool = False, kv_reuse: bool = False, repetition_penalty: Optional[float] = None):
+                 vit_cache: bool = False, prefix_cache: bool = False, kv_reuse: bool = False, repetition_penalty: Optional[float] = None,
+                 answer_constraint=None):
         """Two ways in, both ending in (model, processor, episode state):
           * the reference's: `InternVLAN1Net(config=InternVLAN1ModelConfig(model_cfg={'model': model_settings}))`
             (internvla_n1_agent.py:39-43, internvla_n1_policy.py:29-48) - loads the checkpoint at model_settings['model_path'] on
@@ -1001,6 +1013,10 @@ class InternVLAN1Net:
         # model_settings['repetition_penalty'] (None: the checkpoint's generation_config.json): passed to every System-2 generate() of this env,
         # by s2_step and by the batched agent alike
         self.repetition_penalty = dict(config.model_cfg["model"]).get("repetition_penalty", repetition_penalty) if config is not None else repetition_penalty
+        # model_settings['answer_constraint'] (a constrain.TokenAutomaton, e.g. TokenAutomaton.navigation_answers over the tokenizer's byte
+        # vocabulary; None = unconstrained): passed to every System-2 generate() of this env, by s2_step and by the batched agent alike, so
+        # an answer always parses - no retry of the whole System-2 call for a malformed one
+        self.answer_constraint = dict(config.model_cfg["model"]).get("answer_constraint", answer_constraint) if config is not None else answer_constraint
         self.tokenizer = getattr(processor, "tokenizer", None)
         self.num_history, self.resize_w, self.resize_h, self.continuous_traj = num_history, resize_w, resize_h, continuous_traj
         self.device = model.device
@@ -1039,7 +1055,8 @@ class InternVLAN1Net:
         """a fresh episode state on the same model / processor (the batched agent keeps one per environment)."""
         return InternVLAN1Net(processor=self.processor, num_history=self.num_history, resize_w=self.resize_w, resize_h=self.resize_h,
                               continuous_traj=self.continuous_traj, frame_preprocessor=self.pre, model=self.model, vit_cache=self.vit_cache,
-                              prefix_cache=self.prefix_cache, kv_reuse=self.kv_reuse, repetition_penalty=self.repetition_penalty)
+                              prefix_cache=self.prefix_cache, kv_reuse=self.kv_reuse, repetition_penalty=self.repetition_penalty,
+                              answer_constraint=self.answer_constraint)
 
     def eval(self):
         return self
@@ -1231,7 +1248,9 @@ class InternVLAN1Net:
             past = [past] if past is not None else None
         if self.repetition_penalty is not None:
             extra["repetition_penalty"] = float(self.repetition_penalty)
-        want_lp = bool(getattr(getattr(self.model, "qwen", None), "token_logprobs", False))
+        if self.answer_constraint is not None:
+            extra["constraint"] = self.answer_constraint
+        want_lp =bool(getattr(getattr(self.model, "qwen", None), "token_logprobs", False))
         if want_lp:
             extra["output_logprobs"] = True
         res = self.model.generate(input_ids=inputs["input_ids"], pixel_values=inputs["pixel_values"], image_grid_thw=inputs["image_grid_thw"],

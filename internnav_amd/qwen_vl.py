@@ -412,6 +412,9 @@ class QwenVLEngine:
         # shared-prompt sampling (prefill(sampling=dict(share_prefix=True))): row-count-sized twins of logits / next_tok / seen / xl / hl / _smp_lp
         # and the per-layer answer tails, allocated by the first such call (`_shared_buffers`)
         self._shared = None
+        # constrained decoding (plan(constraint=)): the rows' automaton states, int32 [2, max_seqs] - step `col` reads row col & 1 and writes the
+        # other (ops.automaton_mask_rows needs distinct buffers). Allocated by the first constrained call; the shared-prompt twins carry their own.
+        self._cstate = None
         if self.token_logprobs:
             self._lp_steps, self._mg_steps = (torch.zeros(self.max_decode, max_seqs, dtype=f32, device=dev) for _ in range(2))
             self.tok_logprob, self.tok_margin = self._lp_steps.t(), self._mg_steps.t()
@@ -445,6 +448,7 @@ class QwenVLEngine:
         t.layers = [dict(L, kv=torch.empty_like(L["kv"])) for L in self.layers]
         t._side = None
         t._shared = None
+        t._cstate = None
         t._kv_reset_tracking()
         return t
 
@@ -721,7 +725,7 @@ class QwenVLEngine:
         return self.x[: P * m]
 
     def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None, penalty: Optional[float] = None, col: int = 0,
-                     sampling: Optional[dict] = None, src: Optional[torch.Tensor] = None, bufs=None):
+                     sampling: Optional[dict] = None, src: Optional[torch.Tensor] = None, bufs=None, constraint=None):
         """final RMSNorm + lm_head on ONE row per sequence, greedy argmax on the device. row_in_seq: the same row for every sequence,
         or (ragged batches) rows_idx int32 [B] = absolute row of each sequence's last real token. penalty: the selection runs over the
         repetition-penalised logits of the tokens in `seen` and marks the chosen one (`logits` keeps the raw values).
@@ -730,7 +734,13 @@ class QwenVLEngine:
         row `col` of the state's uniform table; the draw's log-probability goes to column col of the sampling buffer. src int32 [B * K]: the
         output rows (one per returned sequence, with its own seen set) read the B logits rows through it.
         bufs: the buffer set of the selection - logits, next_tok, seen, xl, hl, _smp_lp; None = the engine's own (sized by max_seqs), else the
-        row-count-sized twins of the shared-prompt path (`_shared_buffers`)."""
+        row-count-sized twins of the shared-prompt path (`_shared_buffers`).
+        constraint (a constrain.TokenAutomaton; None = the launch sequence it always was): ONE more launch in front of the selection,
+        ops.automaton_mask_rows on the logits rows - col 0: every row in the start state (a device fill of the state buffer, part of the
+        launch sequence like `_seen_init`: a captured graph re-initialises on replay; with `src` the B logits rows are masked once and all
+        B * K row states start there); col > 0: every row's state advances by the token the previous selection left in next_tok. `logits`
+        then holds -inf at the banned entries. HF's order is penalty, prefix constraint, warpers; the penalty is elementwise and keeps
+        -inf, so masking first and penalising inside the unchanged selection kernels gives the same result."""
         bf = self if bufs is None else bufs
         if rows_idx is not None:
             ops.gather_rows(self.x[: B * S], bf.xl[:B], src=rows_idx)
@@ -741,6 +751,13 @@ class QwenVLEngine:
             ops.linear_w8(bf.hl[:B], *self.lm_head8, out=bf.logits[:B])
         else:
             ops.linear(bf.hl[:B], self.lm_head, out=bf.logits[:B])     # (152064 columns: one wave per 16-column tile owns all of K)
+        if constraint is not None:
+            tb, st = constraint.to(self.device), bf._cstate
+            if col == 0:
+                st.fill_(constraint.start)
+                ops.automaton_mask_rows(bf.logits[:B], tb, st[0, :B], None, st[1, :B])
+            else:
+                ops.automaton_mask_rows(bf.logits[:B], tb, st[col & 1, :B], bf.next_tok[:B], st[(col + 1) & 1, :B])
         if sampling is not None:
             R = B if src is None else src.numel()
             assert col < sampling["u"].shape[0] and col < bf._smp_lp.shape[0] and R <= sampling["u"].shape[1], (col, R, sampling["u"].shape)
@@ -807,7 +824,7 @@ class QwenVLEngine:
         self._shared = SimpleNamespace(
             rows=rows, T=T, logits=torch.empty(rows, self.cfg["vocab"], dtype=f32, device=dev), next_tok=torch.empty(rows, dtype=torch.int32, device=dev),
             seen=torch.zeros(rows, self.seen.shape[1], dtype=torch.uint32, device=dev), xl=torch.empty(rows, self.H, dtype=f32, device=dev),
-            hl=torch.empty(rows, self.H, dtype=bf, device=dev), _smp_lp=torch.zeros(T, rows, dtype=f32, device=dev),
+            hl=torch.empty(rows, self.H, dtype=bf, device=dev), _smp_lp=torch.zeros(T, rows, dtype=f32, device=dev), _cstate=None,
             tails=[torch.empty(rows * T, self.kv_w, dtype=bf, device=dev) for _ in self.layers])
         return self._shared
 
@@ -842,13 +859,20 @@ class QwenVLEngine:
                     shared=dict(tails=bufs.tails, T=bufs.T, kv_dst=i32(np.arange(R) * bufs.T + t), tail_len=i32(np.full(R, t + 1)),
                                 tile_rows=sh["tile_rows"], tile_slot=sh["tile_slot"], tile_pfx=sh["tile_pfx"], max_pfx=sh["max_pfx"]))
 
+    def _constraint_buffers(self, bufs=None):
+        """the automaton-state pair of a buffer set (the engine's own, or the shared-prompt twins: a grown set of twins starts without one)"""
+        bf = self if bufs is None else bufs
+        rows = self.B_max if bufs is None else bufs.rows
+        if bf._cstate is None or bf._cstate.shape[1] < rows:
+            bf._cstate = torch.zeros(2, rows, dtype=torch.int32, device=self.device)
+
     def _seen_init(self, P: dict):
         """launch in front of a decode's first selection: every sequence's seen set = its whole prompt (cached prefix included)"""
         ops.token_seen_set(self.seen, P["rep_ids"], P["rep_lens"], self.cfg["vocab"])
 
     # ---- plan / run: all host work up front, then a pure launch sequence (hipGraph capturable)
     def plan(self, input_ids, image_grid_thw, n_decode: int = 0, with_latents: bool = False, cached_embeds: Optional[list] = None,
-             prefix_len=0, repetition_penalty: float = 1.0, seq_lens=None) -> dict:
+             prefix_len=0, repetition_penalty: float = 1.0, seq_lens=None, constraint=None) -> dict:
         """Host-side plan of one S2 call for B equal-length prompts: embedding / scatter indices, vision plan, position ids and cache
         rows of the prefill, of every decode step and of the latent-query pass (fixed-length answers of n_decode tokens).
         cached_embeds: one entry per image (prompt order over the batch), None = run the vision tower on it, else its merged embeddings
@@ -864,8 +888,16 @@ class QwenVLEngine:
         repetition_penalty (generation_config.json; HF RepetitionPenaltyLogitsProcessor): != 1.0 makes every greedy selection of the decode
         run over the penalised logits of the tokens seen so far - the WHOLE prompt (image placeholders and tokens whose K/V came from a
         cache included; seq_lens [B] real tokens of right-padded prompts) plus the answer. The plan then uploads the full ids [B, S] and the
-        lengths; with 1.0 nothing is uploaded and the launch sequence is the plain one."""
+        lengths; with 1.0 nothing is uploaded and the launch sequence is the plain one.
+        constraint (a constrain.TokenAutomaton over this vocabulary; None = unconstrained, nothing allocated, every launch what it was):
+        every selection of run_decode / decode runs behind ops.automaton_mask_rows (`_last_logits`). The tables are uploaded and the state
+        buffers allocated HERE, so the launch sequence stays capturable."""
         cfg, dev = self.cfg, self.device
+        if constraint is not None:
+            if getattr(constraint, "vocab", None) != cfg["vocab"]:
+                raise ValueError(f"constraint: an automaton over {getattr(constraint, 'vocab', None)} tokens, this model has {cfg['vocab']}")
+            constraint.to(dev)
+            self._constraint_buffers()
         pen = float(repetition_penalty)
         if not (np.isfinite(pen) and pen > 0.0):
             raise ValueError(f"repetition_penalty={repetition_penalty!r}: HF requires a strictly positive float")
@@ -897,6 +929,8 @@ class QwenVLEngine:
             P["rep_penalty"] = pen
             P["rep_ids"] = torch.from_numpy(ids.astype(np.int32)).to(dev)
             P["rep_lens"] = torch.from_numpy(lens.astype(np.int32)).to(dev)
+        if constraint is not None:
+            P["constraint"] = constraint
         img_pos = np.nonzero(flat == cfg["image_token_id"])[0].astype(np.int32)
         if grids:
             ntok_all = [t * h * w // 4 for t, h, w in grids]
@@ -1040,17 +1074,18 @@ class QwenVLEngine:
         if n == 0 or j0 >= j1:
             return
         pen = P.get("rep_penalty")
+        cst = {} if P.get("constraint") is None else {"constraint": P["constraint"]}
         if j0 == 0:
             if pen is not None:
                 self._seen_init(P)                                # part of the launch sequence: a captured decode re-initialises the set on replay
-            self._last_logits(B, S, S - 1, penalty=pen, col=0)
+            self._last_logits(B, S, S - 1, penalty=pen, col=0, **cst)
         for j in range(j0, j1):
             tokens_out[:, j].copy_(self.next_tok[:B])
             if j == n - 1:
                 break
             ops.gather_rows(self.embed, self.x_in, src=self.next_tok[:B], rows=B)
             self._layers(P["decode"][j])
-            self._last_logits(B, 1, 0, penalty=pen, col=j + 1)
+            self._last_logits(B, 1, 0, penalty=pen, col=j + 1, **cst)
 
     def run_latents(self, P: dict, out: torch.Tensor):
         """N_QUERY latent queries (behind the last sampled token) against the KV cache -> out bf16 [B, N_QUERY, H]."""
@@ -1190,7 +1225,7 @@ class QwenVLEngine:
 
     # ---- eager, stateful API (used by the policy layer: answers have data-dependent lengths)
     def prefill(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor], image_grid_thw, cached_embeds: Optional[list] = None,
-                seq_lens=None, prefix_len: int = 0, repetition_penalty: float = 1.0, sampling: Optional[dict] = None) -> dict:
+                seq_lens=None, prefix_len: int = 0, repetition_penalty: float = 1.0, sampling: Optional[dict] = None, constraint=None) -> dict:
         """seq_lens [B] (optional): RAGGED batch - input_ids is right-padded to a common length S and sequence b has seq_lens[b] real
         tokens. Causal attention keeps every real position independent of the padding behind it, so the prefill runs on the padded
         rectangle; the first token is read at each sequence's own last position and the decode / latent passes append at per-sequence
@@ -1206,11 +1241,14 @@ class QwenVLEngine:
         prefill; row b * K + c appends the k|v of its answer tokens to a small tail of its own and ops.attention_shared reads prompt b in
         place (`_share_out`). The selection runs on row-count-sized twins of the max_seqs-sized buffers (`_shared_buffers`, allocated by the
         first such call). Capacity: B <= max_seqs and B * K <= SKINNY_GEMM_MAX_ROWS, else CapacityError before anything is launched.
-        plan() / run_decode (the graph path) stay greedy."""
+        plan() / run_decode (the graph path) stay greedy.
+        constraint: as in `plan` - greedy and sampled decoding alike; each returned sequence keeps an automaton state of its own."""
         if sampling is not None:
             sampling = self._sampling_state(sampling, input_ids.shape[0])
         P = self.plan(input_ids, image_grid_thw, cached_embeds=cached_embeds, prefix_len=prefix_len, repetition_penalty=repetition_penalty,
-                      seq_lens=seq_lens)
+                      seq_lens=seq_lens, **({} if constraint is None else {"constraint": constraint}))
+        if constraint is not None and sampling is not None and sampling.get("share_prefix"):
+            self._constraint_buffers(self._shared)
         self.run_prefill(P, pixel_values)
         st = self.prefill_state(P, input_ids, image_grid_thw, seq_lens)
         if sampling is not None:
@@ -1274,6 +1312,7 @@ class QwenVLEngine:
         out =torch.empty(B * K, n_steps, dtype=torch.int32, device=self.device)
         lens = state.get("lens")
         pen = state["plan"].get("rep_penalty")
+        cst = {} if state["plan"].get("constraint") is None else {"constraint": state["plan"]["constraint"]}
         if smp is not None and state.get("n_sel", 1) + n_steps - 1 > smp["u"].shape[0]:          # before anything is launched
             raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} exceeds the {smp['u'].shape[0]} rows of the sampling state's uniform table")
         if self.token_logprobs and state.get("n_sel", 1) + n_steps - 1 > self.max_decode:      # before anything is launched
@@ -1283,6 +1322,7 @@ class QwenVLEngine:
             if pen is not None:
                 self._seen_init(state["plan"])
             kw = {} if smp is None else {"sampling": smp}
+            kw.update(cst)
             if share:
                 kw["bufs"] = bufs
             if K > 1 or share:
@@ -1321,7 +1361,7 @@ class QwenVLEngine:
                 self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur))
             else:
                 self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur, k_len=cur + 1))
-            self._last_logits(B, 1, 0, penalty=pen, col=state["n_sel"], **({} if smp is None else {"sampling": smp}), **({"bufs": bufs} if share else {}))
+            self._last_logits(B, 1, 0, penalty=pen, col=state["n_sel"], **({} if smp is None else {"sampling": smp}), **({"bufs": bufs} if share else {}), **cst)
             state["n_sel"] += 1
             state["cur"] = cur + 1
             state["next_pos"] = state["next_pos"] + 1
@@ -1397,10 +1437,11 @@ class QwenVLEngine:
 
     # ------------------------------------------------------------------------------------------------ HF-style surface
     def generate(self, input_ids, pixel_values=None, image_grid_thw=None, max_new_tokens: int = 8, eos_token_id=None,
-                 repetition_penalty: float = 1.0, **_):
+                 repetition_penalty: float = 1.0, constraint=None, **_):
         """greedy generate: returns sequences int64 [B, S + n] (a row that reached EOS keeps EOS), n = max_new_tokens.
-        eos_token_id: an int or a list (any member ends a row; the row is filled with the first); repetition_penalty as in `plan`."""
-        state = self.prefill(input_ids, pixel_values, image_grid_thw, repetition_penalty=repetition_penalty)
+        eos_token_id: an int or a list (any member ends a row; the row is filled with the first); repetition_penalty and constraint as in `plan`."""
+        state = self.prefill(input_ids, pixel_values, image_grid_thw, repetition_penalty=repetition_penalty,
+                             **({} if constraint is None else {"constraint": constraint}))
         toks = self.decode(state, max_new_tokens).cpu().long()
         eos_all = eos_ids(self.cfg["eos_token_id"] if eos_token_id is None else eos_token_id)
         eos = eos_all[0]
