@@ -574,6 +574,48 @@ int ina_sample_rows(const float* X, int32_t ldx, int32_t x_rows, int32_t rows, i
 int ina_automaton_mask_rows(float* X, int32_t ldx, int32_t rows, int32_t n, const uint8_t* token_class, int32_t vocab, const uint32_t* allow,
                             const uint8_t* next, int32_t n_states, const int32_t* state_in, const int32_t* prev_tok, int32_t* state_out, void* stream);
 
+/* ---- beam search of System-2 decoding (decode_beam.hip): transformers' GenerationMixin._beam_search as three launches per step, K = num_beams
+ *      hypotheses per prompt in rows b * K .. b * K + K - 1, M = max(2, 1 + n_eos) * K candidates per prompt. tests/beam_ref.py restates the rules.
+ *
+ *  beam_topm_rows: per output row r (logits row s = src ? src[r] : r of X f32 [x_rows, ldx]; seen, run_score and the outputs are indexed by r):
+ *   y = log_softmax(X[s]) in fp32 (expf / logf); with seen, the repetition penalty ON y - bit i of seen[r] set: y < 0 ? y * penalty : y / penalty
+ *   (HF runs its logits processors on the log-probabilities in beam search); acc = y + run_score[r]. cand_score / cand_tok [rows, M]: the M best
+ *   entries by (acc descending, token id ascending). A NaN logit counts as -inf; a row without a number has every y = -inf; a NaN acc counts
+ *   as -inf; -inf entries fill up in id order. +inf logits are not supported. A src outside [0, x_rows) is never accessed: scores -inf, ids
+ *   0 .. M-1. X and seen are only read. No atomics: two launches give the same bits. 2 <= M <= min(32, n), rows <= 65535.
+ *
+ *  beam_step: one workgroup per prompt. cand_* [B * K, M] as beam_topm_rows wrote them. step = index of the answer token this step selects
+ *   (L = step + 1); step 0 starts the prompt: running scores [0, -1e9, ...], an empty finished set, heuristic flag on, not done - whatever the
+ *   buffers hold - and merges row b * K only. A prompt whose done[b] != 0 (step > 0) is frozen: nothing of it is written.
+ *   candidates  the M best of the K rows' lists by (score descending, beam * V + token ascending)
+ *   hit         token in eos[0 .. n_eos), or L == max_new_tokens
+ *   running     the K best by score + hit * -1e9 (ties by position) -> next_tok / parent (GLOBAL row b * K + beam) / run_score [B * K], the token
+ *               histories hist_out [B * K, T] and per-token transition scores ts_out (score - the parent's running score) gathered by parent from
+ *               hist_in / ts_in (the other buffer of a pair) with the new token appended at column step
+ *   finished    fin_tok / fin_ts [B * K, T], fin_score / fin_len / fin_flag [B * K], best first: old entries, then the candidates with score / L **
+ *               length_penalty, + -1e9 when the heuristic flag is off, + -1e9 when early_stopping is 1 and the set was full, + -1e9 when the
+ *               candidate did not hit or is not among the first K; the K best stay (ties by position)
+ *   heur[b]     &= any_k(run_score[0] / H ** length_penalty > (fin_flag[k] ? min(fin_score) : -1e9)), H = max_new_tokens when early_stopping is
+ *               2 ("never") and length_penalty > 0, else L
+ *   done[b]     = heur off, or early_stopping 1 and all K finished, or all M candidates hit
+ *   All arithmetic is HF's, in fp32. early_stopping: 0 False, 1 True, 2 "never". K <= 8, K <= M <= 32, n_eos <= 8, step < max_new_tokens <= T.
+ *
+ *  beam_reorder: re-parents the per-row state in front of the next pass. For layer l < n_layers the first t rows of the T-row tail of row r at
+ *   dst_base[l] + r * T * row_bytes come from row parent[r] at src_base[l] (device tables of addresses; the two sets must not overlap;
+ *   row_bytes % 16 == 0); seen_dst[r] = seen_src[parent[r]] | bit next_tok[r] (ld_words words per row; a token outside [0, n) marks nothing);
+ *   state_dst[r] = state_src[parent[r]]. seen_* / state_* may be NULL in pairs. A parent outside [0, rows) copies nothing for its row and causes
+ *   no access.
+ *  Refusals return non-zero before any HIP call. Plain arguments: no struct, no ABI bump. */
+int ina_beam_topm_rows(const float* X, int32_t ldx, int32_t x_rows, int32_t rows, int32_t n, const uint32_t* seen, int32_t ld_words, float penalty,
+                       const float* run_score, const int32_t* src, int32_t M, float* cand_score, int32_t* cand_tok, void* stream);
+int ina_beam_step(const float* cand_score, const int32_t* cand_tok, int32_t B, int32_t K, int32_t M, int32_t T, int32_t step, int32_t max_new_tokens,
+                  float length_penalty, int32_t early_stopping, const int32_t* eos, int32_t n_eos, float* run_score, int32_t* next_tok, int32_t* parent,
+                  const int32_t* hist_in, int32_t* hist_out, const float* ts_in, float* ts_out, int32_t* fin_tok, float* fin_ts, float* fin_score,
+                  int32_t* fin_len, int32_t* fin_flag, int32_t* heur, int32_t* done, void* stream);
+int ina_beam_reorder(const int64_t* src_base, const int64_t* dst_base, int32_t n_layers, const int32_t* parent, int32_t rows, int32_t T, int32_t t,
+                     int64_t row_bytes, const uint32_t* seen_src, uint32_t* seen_dst, int32_t ld_words, const int32_t* next_tok, int32_t n,
+                     const int32_t* state_src, int32_t* state_dst, void* stream);
+
 /* ---- select_traj: per env, rank the S samples by critic value; neg = the k lowest (ascending), pos = the k highest
  *      (descending); trajectories are cumsum_t(sample * scale).  reference: navdp_policy.py:317-320. */
 typedef struct ina_select_args {

@@ -318,6 +318,12 @@ SYMBOLS = {
                                    c_void_p]),
     "ina_sample_rows": (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, C.c_float, c_int32, C.c_float, c_int32, C.c_float,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ina_beam_topm_rows": (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, C.c_float, c_void_p, c_void_p, c_int32, c_void_p,
+                                     c_void_p, c_void_p]),
+    "ina_beam_step": (C.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, C.c_float, c_int32, c_void_p, c_int32] +
+                      [c_void_p] * 15),
+    "ina_beam_reorder": (C.c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_int32, c_void_p,
+                                   c_int32, c_void_p, c_void_p, c_void_p]),
     "ina_automaton_mask_rows": (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                           c_void_p]),
     "ina_dit_attention": (C.c_int, [C.POINTER(DitAttnArgs), c_void_p]),

@@ -257,6 +257,61 @@ int ina_logprob_rows(const float* X, int32_t ldx, int32_t rows, int32_t n, uint3
     return ina_launch_logprob(X, ldx, rows, n, seen, ld_words, penalty, mark, target, tok, logprob, margin, reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_beam_topm_rows(const float* X, int32_t ldx, int32_t x_rows, int32_t rows, int32_t n, const uint32_t* seen, int32_t ld_words, float penalty,
+                       const float* run_score, const int32_t* src, int32_t M, float* cand_score, int32_t* cand_tok, void* stream) {
+    INA_REQUIRE(X && run_score && cand_score && cand_tok, "beam_topm_rows: X, run_score, cand_score and cand_tok required");
+    INA_REQUIRE(rows >= 0 && rows <= 65535 && x_rows >= 1 && n >= 1 && ldx >= n,
+                "beam_topm_rows: bad arguments rows=%d x_rows=%d n=%d ldx=%d (0 <= rows <= 65535, x_rows >= 1, n >= 1, ldx >= n)", rows, x_rows, n, ldx);
+    INA_REQUIRE(src || rows <= x_rows, "beam_topm_rows: rows=%d output rows of x_rows=%d logits rows need a src table", rows, x_rows);
+    INA_REQUIRE(M >= 2 && M <= 32 && M <= n, "beam_topm_rows: M=%d candidates per row outside [2, min(32, n=%d)]", M, n);
+    if (seen) {
+        INA_REQUIRE((long)ld_words * 32 >= (long)n, "beam_topm_rows: ld_words=%d holds fewer than n=%d bits", ld_words, n);
+        INA_REQUIRE(std::isfinite(penalty) && penalty > 0.f, "beam_topm_rows: repetition penalty %g is not a strictly positive finite float", (double)penalty);
+    }
+    if (rows == 0) return 0;
+    return ina_launch_beam_topm(X, ldx, x_rows, rows, n, seen, ld_words, penalty, run_score, src, M, cand_score, cand_tok,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+int ina_beam_step(const float* cand_score, const int32_t* cand_tok, int32_t B, int32_t K, int32_t M, int32_t T, int32_t step, int32_t max_new_tokens,
+                  float length_penalty, int32_t early_stopping, const int32_t* eos, int32_t n_eos, float* run_score, int32_t* next_tok, int32_t* parent,
+                  const int32_t* hist_in, int32_t* hist_out, const float* ts_in, float* ts_out, int32_t* fin_tok, float* fin_ts, float* fin_score,
+                  int32_t* fin_len, int32_t* fin_flag, int32_t* heur, int32_t* done, void* stream) {
+    INA_REQUIRE(cand_score && cand_tok && run_score && next_tok && parent && hist_in && hist_out && ts_in && ts_out && fin_tok && fin_ts && fin_score &&
+                    fin_len && fin_flag && heur && done, "beam_step: every buffer but eos is required");
+    INA_REQUIRE(B >= 0 && B <= 65535 && K >= 1 && K <= 8 && M >= 2 && M >= K && M <= 32,
+                "beam_step: bad arguments B=%d K=%d M=%d (0 <= B <= 65535, 1 <= K <= 8, max(2, K) <= M <= 32)", B, K, M);
+    INA_REQUIRE(max_new_tokens >= 1 && max_new_tokens <= T && step >= 0 && step < max_new_tokens,
+                "beam_step: step=%d max_new_tokens=%d T=%d (0 <= step < max_new_tokens <= T)", step, max_new_tokens, T);
+    INA_REQUIRE(n_eos >= 0 && n_eos <= 8 && (n_eos == 0 || eos), "beam_step: n_eos=%d outside [0, 8], or no table", n_eos);
+    INA_REQUIRE(std::isfinite(length_penalty), "beam_step: length_penalty %g is not finite", (double)length_penalty);
+    INA_REQUIRE(early_stopping >= 0 && early_stopping <= 2, "beam_step: early_stopping mode %d (0 False, 1 True, 2 never)", early_stopping);
+    INA_REQUIRE(hist_in != hist_out && ts_in != ts_out, "beam_step: the histories are read from one buffer of a pair and written to the other");
+    if (B == 0) return 0;
+    // HF's python-float powers, rounded to fp32 once: the answer length of this step, and the heuristic's hypothetical length
+    const double L = (double)(step + 1), H = (early_stopping == 2 && length_penalty > 0.f) ? (double)max_new_tokens : L;
+    const float lenpow = (float)std::pow(L, (double)length_penalty), hyppow = (float)std::pow(H, (double)length_penalty);
+    return ina_launch_beam_step(cand_score, cand_tok, B, K, M, T, step, max_new_tokens, lenpow, hyppow, early_stopping, eos, n_eos, run_score, next_tok,
+                                parent, hist_in, hist_out, ts_in, ts_out, fin_tok, fin_ts, fin_score, fin_len, fin_flag, heur, done,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+int ina_beam_reorder(const int64_t* src_base, const int64_t* dst_base, int32_t n_layers, const int32_t* parent, int32_t rows, int32_t T, int32_t t,
+                     int64_t row_bytes, const uint32_t* seen_src, uint32_t* seen_dst, int32_t ld_words, const int32_t* next_tok, int32_t n,
+                     const int32_t* state_src, int32_t* state_dst, void* stream) {
+    INA_REQUIRE(parent && rows >= 0 && rows <= 65535 && n_layers >= 0 && n_layers < 65535, "beam_reorder: parent required, rows=%d layers=%d", rows, n_layers);
+    INA_REQUIRE(n_layers == 0 || (src_base && dst_base && src_base != dst_base), "beam_reorder: two distinct layer base tables required");
+    INA_REQUIRE(T >= 1 && t >= 0 && t <= T, "beam_reorder: t=%d tail rows of T=%d", t, T);
+    INA_REQUIRE(n_layers == 0 || (row_bytes > 0 && row_bytes % 16 == 0), "beam_reorder: row_bytes=%ld must be a positive multiple of 16", (long)row_bytes);
+    INA_REQUIRE((!seen_src && !seen_dst) || (seen_src && seen_dst && seen_src != seen_dst), "beam_reorder: the seen sets are two distinct buffers, or both NULL");
+    INA_REQUIRE(!seen_src || (next_tok && ld_words >= 1 && n >= 1 && (long)ld_words * 32 >= (long)n),
+                "beam_reorder: the seen gather needs next_tok and ld_words=%d * 32 >= n=%d", ld_words, n);
+    INA_REQUIRE((!state_src && !state_dst) || (state_src && state_dst && state_src != state_dst), "beam_reorder: the automaton states are two distinct buffers, or both NULL");
+    if (rows == 0) return 0;
+    return ina_launch_beam_reorder(src_base, dst_base, n_layers, parent, rows, T, t, (long)row_bytes, seen_src, seen_dst, ld_words, next_tok, n, state_src,
+                                   state_dst, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_sample_rows(const float* X, int32_t ldx, int32_t x_rows, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
                     float temperature, int32_t top_k, float top_p, const float* u, const int32_t* src, int32_t* tok, float* logprob, int32_t* n_kept,
                     float* thr, void* stream) {

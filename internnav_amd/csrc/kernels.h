@@ -96,6 +96,15 @@ int ina_launch_sample(const float* X, int ldx, int x_rows, int rows, int n, uint
                       hipStream_t stream);                                                                                   // decode_sample.hip
 int ina_launch_automaton_mask(float* X, int ldx, int rows, int n, const uint8_t* token_class, int vocab, const uint32_t* allow, const uint8_t* next,
                               int n_states, const int32_t* state_in, const int32_t* prev_tok, int32_t* state_out, hipStream_t stream);   // decode_constrain.hip
+int ina_launch_beam_topm(const float* X, int ldx, int x_rows, int rows, int n, const uint32_t* seen, int ld_words, float penalty, const float* run_score,
+                         const int32_t* src, int M, float* cand_score, int32_t* cand_tok, hipStream_t stream);                 // decode_beam.hip
+int ina_launch_beam_step(const float* cand_score, const int32_t* cand_tok, int B, int K, int M, int T, int step, int max_new, float lenpow, float hyppow,
+                         int early, const int32_t* eos, int n_eos, float* run_score, int32_t* next_tok, int32_t* parent, const int32_t* hist_in,
+                         int32_t* hist_out, const float* ts_in, float* ts_out, int32_t* fin_tok, float* fin_ts, float* fin_score, int32_t* fin_len,
+                         int32_t* fin_flag, int32_t* heur, int32_t* done, hipStream_t stream);
+int ina_launch_beam_reorder(const int64_t* src_base, const int64_t* dst_base, int n_layers, const int32_t* parent, int rows, int T, int t, long row_bytes,
+                            const uint32_t* seen_src, uint32_t* seen_dst, int ld_words, const int32_t* next_tok, int n, const int32_t* state_src,
+                            int32_t* state_dst, hipStream_t stream);
 int ina_launch_head3(const Head3Args& p, hipStream_t stream);
 int ina_launch_seqpool(const SeqpoolArgs& p, hipStream_t stream);
 int ina_launch_select(const SelectArgs& p, hipStream_t stream);

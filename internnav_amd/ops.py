@@ -933,6 +933,90 @@ def automaton_mask_rows(x: torch.Tensor, tables, state_in: torch.Tensor, prev_to
     return x
 
 
+BEAM_MAX_CANDIDATES = 32      # M of beam_topm_rows / beam_step: max(2, 1 + n_eos) * num_beams
+BEAM_EARLY = {False: 0, True: 1, "never": 2}
+
+
+def beam_topm_rows(x: torch.Tensor, run_score: torch.Tensor, cand_score: torch.Tensor, cand_tok: torch.Tensor, seen: Optional[torch.Tensor] = None,
+                   penalty: float = 1.0, src: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The candidates of one beam-search step per output row, in one launch: y = log_softmax of the f32 row of x (not modified), with `seen`
+    the repetition penalty ON y (HF's beam search processes log-probabilities: seen ? (y < 0 ? y * p : y / p) : y), acc = y + run_score[r];
+    cand_score f32 / cand_tok int32 [rows, M] = the M best entries by (acc descending, token id ascending), M = cand_score.shape[1] in
+    [2, min(32, n)]. src int32 [rows]: output row r reads x[src[r]] (an entry outside the rows of x: scores -inf, ids 0 .. M-1, no access).
+    A NaN logit counts as -inf; -inf entries fill up in id order. Deterministic: the same inputs give the same bits."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    x_rows, n = x.shape
+    rows = x_rows if src is None else src.numel()
+    assert cand_score.dtype == torch.float32 and cand_score.dim() == 2 and cand_score.is_contiguous() and cand_score.shape[0] == rows
+    assert cand_tok.dtype == torch.int32 and cand_tok.shape == cand_score.shape and cand_tok.is_contiguous()
+    assert run_score.dtype == torch.float32 and run_score.numel() == rows and run_score.is_contiguous()
+    assert src is None or (src.dtype == torch.int32 and src.is_contiguous())
+    if seen is not None:
+        assert seen.dtype in (torch.uint32, torch.int32) and seen.dim() == 2 and seen.stride(1) == 1 and seen.shape[0] >= rows and seen.shape[1] * 32 >= n
+    rc = _lib.lib().ina_beam_topm_rows(x.data_ptr(), x.stride(0) if x_rows > 1 else max(x.stride(0), n), x_rows, rows, n,
+                                       seen.data_ptr() if seen is not None else None, seen.stride(0) if seen is not None else 0, float(penalty),
+                                       run_score.data_ptr(), src.data_ptr() if src is not None else None, cand_score.shape[1], cand_score.data_ptr(),
+                                       cand_tok.data_ptr(), _stream())
+    _lib.check(rc, "beam_topm_rows")
+    return cand_score
+
+
+def beam_step(cand_score: torch.Tensor, cand_tok: torch.Tensor, st, step: int, max_new_tokens: int, length_penalty: float = 1.0, early_stopping=False,
+              flip: Optional[int] = None) -> None:
+    """The bookkeeping of one beam-search step, one workgroup per prompt (include/internnav_amd.h, tests/beam_ref.py): merges the K rows' candidate
+    lists of every prompt, applies transformers' rules in its fp32 arithmetic and writes the next running set and the finished set into `st`,
+    a namespace of device buffers: K, eos int32 [n_eos] (or None), run_score f32 / next_tok / parent int32 [B * K], hist int32 and ts f32
+    [2, B * K, T] (ping-pong pairs, a tensor or two tensors: this step reads half flip, default step & 1, and writes the other), fin_tok int32 / fin_ts f32 [B * K, T],
+    fin_score f32 / fin_len / fin_flag int32 [B * K], heur / done int32 [B]. step 0 initialises the prompts; a done prompt is frozen."""
+    R, M = cand_score.shape
+    K = int(st.K)
+    assert R % K == 0 and cand_score.dtype == torch.float32 and cand_score.is_contiguous()
+    assert cand_tok.dtype == torch.int32 and cand_tok.shape == cand_score.shape and cand_tok.is_contiguous()
+    B, T = R // K, st.hist[0].shape[1]
+    for t, dt, shape in ((st.run_score, torch.float32, (R,)), (st.next_tok, torch.int32, (R,)), (st.parent, torch.int32, (R,)),
+                         (st.hist[0], torch.int32, (R, T)), (st.hist[1], torch.int32, (R, T)), (st.ts[0], torch.float32, (R, T)),
+                         (st.ts[1], torch.float32, (R, T)), (st.fin_tok, torch.int32, (R, T)),
+                         (st.fin_ts, torch.float32, (R, T)), (st.fin_score, torch.float32, (R,)), (st.fin_len, torch.int32, (R,)),
+                         (st.fin_flag, torch.int32, (R,)), (st.heur, torch.int32, (B,)), (st.done, torch.int32, (B,))):
+        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous(), (t.dtype, tuple(t.shape), dt, shape)
+    eos = getattr(st, "eos", None)
+    assert eos is None or (eos.dtype == torch.int32 and eos.is_contiguous())
+    f = (step & 1) if flip is None else int(flip)
+    rc = _lib.lib().ina_beam_step(cand_score.data_ptr(), cand_tok.data_ptr(), B, K, M, T, int(step), int(max_new_tokens), float(length_penalty),
+                                  BEAM_EARLY[early_stopping], eos.data_ptr() if eos is not None else None, eos.numel() if eos is not None else 0,
+                                  st.run_score.data_ptr(), st.next_tok.data_ptr(), st.parent.data_ptr(), st.hist[f].data_ptr(), st.hist[1 - f].data_ptr(),
+                                  st.ts[f].data_ptr(), st.ts[1 - f].data_ptr(), st.fin_tok.data_ptr(), st.fin_ts.data_ptr(), st.fin_score.data_ptr(),
+                                  st.fin_len.data_ptr(), st.fin_flag.data_ptr(), st.heur.data_ptr(), st.done.data_ptr(), _stream())
+    _lib.check(rc, "beam_step")
+
+
+def beam_reorder(parent: torch.Tensor, src_base: Optional[torch.Tensor] = None, dst_base: Optional[torch.Tensor] = None, T: int = 1, t: int = 0,
+                 row_bytes: int = 16, seen_src: Optional[torch.Tensor] = None, seen_dst: Optional[torch.Tensor] = None,
+                 next_tok: Optional[torch.Tensor] = None, n: int = 0, state_src: Optional[torch.Tensor] = None,
+                 state_dst: Optional[torch.Tensor] = None) -> None:
+    """Re-parents the per-row state of a beam search in front of the next pass, one launch: for every layer the first t rows of row r's T-row tail
+    in the destination set come from row parent[r] of the source set (src_base / dst_base: int64 device tables of the layers' tail addresses,
+    two sets that do not overlap); seen_dst[r] = seen_src[parent[r]] | bit next_tok[r] (n = vocabulary); state_dst[r] = state_src[parent[r]].
+    A parent outside [0, rows) leaves its row unwritten. Bit copies."""
+    rows = parent.numel()
+    assert parent.dtype == torch.int32 and parent.is_contiguous()
+    n_layers = 0 if src_base is None else src_base.numel()
+    if n_layers:
+        assert src_base.dtype == torch.int64 and dst_base.dtype == torch.int64 and dst_base.numel() == n_layers and src_base.is_contiguous() and dst_base.is_contiguous()
+    ld = 0
+    if seen_src is not None:
+        ld = seen_src.shape[1]
+        for s in (seen_src, seen_dst):
+            assert s.dtype in (torch.uint32, torch.int32) and s.dim() == 2 and s.is_contiguous() and s.shape[0] >= rows and s.shape[1] == ld
+        assert next_tok.dtype == torch.int32 and next_tok.is_contiguous() and next_tok.numel() >= rows
+    for s in (state_src, state_dst):
+        assert s is None or (s.dtype == torch.int32 and s.is_contiguous() and s.numel() >= rows)
+    p = lambda v: v.data_ptr() if v is not None else None      # noqa: E731
+    rc = _lib.lib().ina_beam_reorder(p(src_base), p(dst_base), n_layers, parent.data_ptr(), rows, int(T), int(t), int(row_bytes), p(seen_src), p(seen_dst),
+                                     ld, p(next_tok), int(n), p(state_src), p(state_dst), _stream())
+    _lib.check(rc, "beam_reorder")
+
+
 def dit_v2t(kv2: torch.Tensor, heads: int, v2t: torch.Tensor) -> torch.Tensor:
     """condition V of a NextDiT block -> the transposed key-permuted image dit_attention consumes.
     kv2 bf16 [envs, Lz, 2, heads, 64] (K | V as produced by the fused kv projection); v2t bf16 [envs, heads, 64, 64]."""

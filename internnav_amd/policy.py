@@ -257,6 +257,50 @@ def sampling_spec(gen_cfg: SimpleNamespace, do_sample: bool, temperature=None, t
     return SimpleNamespace(temperature=T, top_k=tk, top_p=tp, K=K)
 
 
+BEAM_MAX_BEAMS = 8         # num_beams and EOS ids of the beam path: max(2, 1 + n_eos) * num_beams candidates per prompt stay within the 32 of
+BEAM_MAX_EOS = 3           # ops.beam_topm_rows
+
+
+def beam_spec(num_beams=None, num_return_sequences: Optional[int] = None, length_penalty: float = 1.0, early_stopping=False,
+              do_sample: bool = False, share_prefix: Optional[bool] = None, extra: Optional[dict] = None) -> Optional[SimpleNamespace]:
+    """what generate(num_beams=K) searches with, resolved as HF resolves it (host only): None for num_beams None or 1 (today's paths), else a
+    namespace K = num_beams / n = num_return_sequences (default 1) / length_penalty / early_stopping (False, True or "never").
+    ValueError (as HF): num_beams < 1; num_return_sequences > num_beams; a length_penalty that is not finite; early_stopping outside
+    {False, True, "never"}; share_prefix=False passed explicitly (the beams of a prompt always share its one cache slot).
+    NotImplementedError naming the key: do_sample=True with beams (beam sampling), num_beam_groups > 1, a diversity_penalty other than 0,
+    constraints / force_words_ids (`extra` = generate's remaining kwargs). Beam search is opt-in by ARGUMENT only: a generation_config.json
+    that sets num_beams > 1 stays refused at load (`generation_config_from_hf`)."""
+    if num_beams is None:
+        return None
+    K = int(num_beams)
+    if K < 1:
+        raise ValueError(f"num_beams={num_beams!r} must be >= 1")
+    if K == 1:
+        return None
+    extra = extra or {}
+    if do_sample:
+        raise NotImplementedError("generate(num_beams > 1, do_sample=True): beam sampling is not implemented (do_sample=False searches, "
+                                  "num_beams=1 samples)")
+    for k, off in (("num_beam_groups", lambda v: v is None or int(v) == 1), ("diversity_penalty", lambda v: v is None or float(v) == 0.0),
+                   ("constraints", lambda v: v is None), ("force_words_ids", lambda v: v is None)):
+        if not off(extra.get(k)):
+            raise NotImplementedError(f"generate(num_beams > 1): {k}={extra[k]!r} is not implemented (group / diverse / lexically constrained "
+                                      "beam search); constraint= takes a constrain.TokenAutomaton")
+    n = 1 if num_return_sequences is None else int(num_return_sequences)
+    if n < 1:
+        raise ValueError(f"num_return_sequences={num_return_sequences!r} must be >= 1")
+    if n > K:
+        raise ValueError(f"num_return_sequences={n} has to be smaller or equal to num_beams={K} (as HF)")
+    lp = float(length_penalty)
+    if not np.isfinite(lp):
+        raise ValueError(f"length_penalty={length_penalty!r} has to be a finite float")
+    if not any(early_stopping is v for v in (False, True)) and early_stopping != "never":
+        raise ValueError(f"early_stopping={early_stopping!r} must be a boolean or 'never' (as HF)")
+    if share_prefix is not None and not share_prefix:
+        raise ValueError("share_prefix=False with num_beams > 1: the beams of a prompt are decoded behind its one cache slot, there is no other path")
+    return SimpleNamespace(K=K, n=n, length_penalty=lp, early_stopping=early_stopping)
+
+
 SCORE_SLAB_ROWS = 256      # rows of the fp32 [rows, vocab] logit buffer of score_answers (156 MB at 152064 tokens), allocated on first use
 
 
@@ -452,7 +496,8 @@ class InternVLAN1ForCausalLM:
                  export_prefix: Optional[list] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
                  temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  num_return_sequences: Optional[int] = None, generator: Optional[torch.Generator] = None, seed: Optional[int] = None,
-                 share_prefix: bool = False, constraint=None, **kw):
+                 share_prefix: Optional[bool] = None, constraint=None, num_beams: Optional[int] = None, length_penalty: float = 1.0,
+                 early_stopping=False, **kw):
         """greedy decoding by default (do_sample=False is the only mode the reference uses, internvla_n1_policy.py:169-176). Decodes in chunks of
         `decode_chunk` device-side steps and stops once every sequence has emitted EOS. Sequences are right-filled with EOS.
         repetition_penalty / eos_token_id: None = the checkpoint's generation_config.json (`self.generation_config`; without that file 1.0
@@ -503,10 +548,42 @@ class InternVLAN1ForCausalLM:
         advances each row's state by the token it just got and sets the logits of the tokens its state does not allow to -inf; greedy,
         do_sample (num_return_sequences / share_prefix: a state per returned sequence), output_logprobs (the log-softmax over the ALLOWED
         tokens: HF's processed scores) and past_key_values work as without it. At most 256 states and 256 token classes. An answer that
-        max_new_tokens cuts before an accepting state is returned as it is. score_answers is NOT constrained and not renormalised."""
+        max_new_tokens cuts before an accepting state is returned as it is. score_answers is NOT constrained and not renormalised.
+        num_beams=K > 1 (opt-in BY ARGUMENT only; None or 1 = the paths above, launch for launch): transformers' beam search
+        (GenerationMixin._beam_search; tests/beam_ref.py restates its rules) - the K most probable answers of every prompt, deterministic and
+        distinct, decoded behind the prompt's ONE cache slot like share_prefix sampling, with three more launches per step and no host round
+        trip inside a decode_chunk (`QwenVLEngine.prefill(beam=)`). num_return_sequences=n <= K (default 1), length_penalty (default 1.0) and
+        early_stopping (False, True or "never") mean what they mean in HF; repetition_penalty, eos_token_id (at most 3 ids) and constraint
+        work as everywhere. `sequences` is [B * n, S + T], prompt-major, best first, right-filled with the first EOS id; with
+        return_dict_in_generate the result also carries sequences_scores f32 [B * n] (sum of log-probabilities / length ** length_penalty),
+        answer_lengths, valid bool [B * n] (a finished hypothesis with a score above -inf; an invalid row is filled with EOS and scores -inf)
+        and, with output_logprobs=True (any model), token_logprobs [B * n, T]: the hypothesis's per-token transition scores, 0.0 behind its
+        end - their sum / length ** length_penalty is the score. past_key_values is None and export_prefix is refused, as with K > 1 sampling;
+        generate_latents(rows=) on the returned rows runs answer + latent queries as one suffix pass behind the untouched prompt slot.
+        Capacity: B <= max_seqs, B * K <= 64, K <= 8, max_new_tokens <= max_decode; CapacityError before anything is launched.
+        Two documented differences from HF: (1) the repetition penalty acts on log-probabilities here as in HF's beam search, which is NOT what
+        the greedy and sampled paths do (they penalise logits, as HF does there); with constraint= the banned logits are -inf BEFORE the
+        log-softmax, so a score is the log-probability over the allowed tokens, renormalised per step - HF's prefix_allowed_tokens_fn under
+        beams masks behind the softmax and does not renormalise; a hypothesis that had to take a banned token stays at -inf and is not valid.
+        (2) a generation_config.json that sets num_beams > 1 stays refused at load: the agent's captured plan() / run_decode chain is greedy.
+        Refused (as HF / NotImplementedError naming the key): `beam_spec`."""
         if constraint is not None and getattr(constraint, "vocab", None) != self.qwen.cfg["vocab"]:
             raise ValueError(f"constraint: an automaton over {getattr(constraint, 'vocab', None)} tokens, this model has {self.qwen.cfg['vocab']}")
-        smp = sampling_spec(self.generation_config, do_sample, temperature, top_k, top_p, num_return_sequences, kw)
+        bms = beam_spec(num_beams, num_return_sequences, length_penalty, early_stopping, do_sample, share_prefix, kw)
+        share_prefix = bool(share_prefix) and bms is None
+        smp = sampling_spec(self.generation_config, do_sample, temperature, top_k, top_p, None if bms is not None else num_return_sequences, kw)
+        if bms is not None:                                      # every refusal of the beam path before anything is launched
+            n_eos = len(self.generation_config.eos_token_id if eos_token_id is None else eos_ids(eos_token_id))
+            if export_prefix is not None and any(export_prefix):
+                raise ValueError("export_prefix is not supported with num_beams > 1: export the prefix from a call with one sequence per prompt")
+            if input_ids.shape[0] > self.qwen.B_max or input_ids.shape[0] * bms.K > SKINNY_GEMM_MAX_ROWS:
+                raise CapacityError(f"{input_ids.shape[0]} prompts x num_beams={bms.K} exceed the engine's max_seqs={self.qwen.B_max} prompts or the "
+                                    f"{SKINNY_GEMM_MAX_ROWS} rows of a single-token pass")
+            if bms.K > BEAM_MAX_BEAMS or n_eos > BEAM_MAX_EOS:
+                raise CapacityError(f"num_beams={bms.K} with {n_eos} EOS ids: the beam path takes at most {BEAM_MAX_BEAMS} beams and {BEAM_MAX_EOS} EOS ids")
+            if max_new_tokens > self.qwen.max_decode:
+                raise CapacityError(f"max_new_tokens={max_new_tokens} exceeds the engine's max_decode={self.qwen.max_decode}: build the model with a "
+                                    "larger max_decode (from_pretrained(..., max_decode=N))")
         if share_prefix and smp is None:
             raise ValueError("share_prefix=True needs do_sample=True: greedy decoding returns one sequence per prompt and has nothing to share")
         if smp is not None:
@@ -522,7 +599,7 @@ class InternVLAN1ForCausalLM:
             if max_new_tokens > self.qwen.max_decode:
                 raise CapacityError(f"max_new_tokens={max_new_tokens} exceeds the max_decode={self.qwen.max_decode} log-probability columns of the "
                                     "sampling path: build the model with a larger max_decode (from_pretrained(..., max_decode=N))")
-        if output_logprobs and smp is None and not self.qwen.token_logprobs:
+        if output_logprobs and smp is None and bms is None and not self.qwen.token_logprobs:
             raise ValueError("generate(output_logprobs=True) needs the engine setting token_logprobs: build the model with "
                              "token_logprobs=True (from_pretrained(..., token_logprobs=True) / model_settings['token_logprobs'] = True)")
         if self.qwen.token_logprobs and max_new_tokens > self.qwen.max_decode:
@@ -565,13 +642,17 @@ class InternVLAN1ForCausalLM:
                 pv = torch.cat(keep, 0) if keep else None
         state = self.qwen.prefill(input_ids, pv, image_grid_thw, cached_embeds=cached_image_embeds, seq_lens=plens if attention_mask is not None else None,
                                   prefix_len=pl, **({} if penalty == 1.0 else {"repetition_penalty": penalty}), **self._sampling_kw(smp, B, max_new_tokens, generator, seed, share_prefix),
-                                  **({} if constraint is None else {"constraint": constraint}))
+                                  **({} if constraint is None else {"constraint": constraint}),
+                                  **({} if bms is None else {"beam": dict(K=bms.K, max_new_tokens=max_new_tokens, eos=eos_all, length_penalty=bms.length_penalty,
+                                                                          early_stopping=bms.early_stopping)}))
         self._prefix_out = {}
         if export_prefix is not None:
             for b, n in enumerate(export_prefix):
                 if n:
                     self._prefix_out[b] = self.qwen.export_prefix_kv(b, int(n))
         self._fresh = self.qwen.fresh_image_embeds(state["plan"]) if cached_image_embeds is not None else {}
+        if bms is not None:
+            return self._finish_beams(state, bms, input_ids, plens, max_new_tokens, decode_chunk, eos, return_dict_in_generate, output_logprobs)
         chunks, n = [], 0
         while n < max_new_tokens:
             k = min(decode_chunk, max_new_tokens - n)
@@ -622,6 +703,42 @@ class InternVLAN1ForCausalLM:
         keep = plens if exact else np.broadcast_to(np.asarray(pl, dtype=np.int64), (B,))
         pkv = self.qwen.kv_handle([ids_cpu[b, : int(keep[b])] for b in range(B)]) if use_cache and not fanned else None
         return SimpleNamespace(sequences=seqs, past_key_values=pkv, **lp_out)
+
+    def _finish_beams(self, state, bms, input_ids, plens, max_new_tokens: int, decode_chunk: int, eos: int, as_dict: bool, with_logprobs: bool):
+        """the decode loop and the outputs of generate(num_beams=K): chunks of device-side steps, ONE host read (the prompts' done flags) per chunk"""
+        n = 0
+        while n < max_new_tokens:
+            k = min(decode_chunk, max_new_tokens - n)
+            self.qwen.decode(state, k + 1 if n else k)           # later chunks re-emit the pending tokens first
+            n += k
+            if bool(self.qwen.beam_done(state).all()):
+                break
+        res = self.qwen.beam_results(state)
+        B, S = input_ids.shape
+        K, nr = bms.K, bms.n
+        valid = (res.finished & (res.scores > -float("inf")))[:, :nr].reshape(-1)
+        lens = torch.where(valid, res.lengths[:, :nr].reshape(-1), torch.zeros((), dtype=torch.long))
+        scores = torch.where(valid, res.scores[:, :nr].reshape(-1), torch.full((), -float("inf")))
+        T = max(1, int(lens.max()))
+        cols = torch.arange(T).view(1, T)
+        inside = cols < lens.view(-1, 1)
+        toks = torch.where(inside, res.tokens[:, :nr, :T].reshape(B * nr, T), torch.full((), eos, dtype=torch.long))
+        ids_cpu = input_ids.cpu().long().repeat_interleave(nr, dim=0)
+        pl = np.repeat(plens, nr)
+        seqs = torch.full((B * nr, S + T), eos, dtype=torch.long)
+        for r in range(B * nr):
+            L = int(pl[r])
+            seqs[r, :L] = ids_cpu[r, :L]
+            seqs[r, L:L + T] = toks[r]
+        # what generate_latents continues: the prompts' slots, which the search never wrote (qwen.latents_after)
+        self._gen = dict(state=state, tokens=toks, lens=lens.numpy(), prompt_lens=pl, fanned=True, path="beam", prompt_of=np.repeat(np.arange(B), nr))
+        seqs = seqs.to(self.device)
+        if not as_dict:
+            return seqs
+        out = dict(sequences=seqs, past_key_values=None, sequences_scores=scores.to(self.device), answer_lengths=lens.to(self.device), valid=valid.to(self.device))
+        if with_logprobs:
+            out["token_logprobs"] = torch.where(inside, res.token_scores[:, :nr, :T].reshape(B * nr, T), torch.zeros(())).to(self.device)
+        return SimpleNamespace(**out)
 
     def _sampling_kw(self, smp, B: int, max_new_tokens: int, generator, seed, share_prefix: bool = False) -> dict:
         """the engine's sampling spec of one generate() call ({} = greedy): the uniforms of every step and returned sequence, drawn HERE on
@@ -842,14 +959,24 @@ class InternVLAN1ForCausalLM:
         in its cache slot and the row's own answer K/V (its slot on the fan-out path, its tail on the shared-prefix path), read in place
         (`QwenVLEngine.latents_behind`, ops.attention_prefix_tail) - no ViT, no prefill, nothing written, so the call can be repeated and
         made for other rows. The requested rows' answers must equal the tokens generate() returned (up to the common width); anything
-        else - other tokens, another row count, a score_answers() call in between - takes the re-run path, as before."""
+        else - other tokens, another row count, a score_answers() call in between - takes the re-run path, as before.
+        After generate(num_beams=K) (output_ids = its B * num_return_sequences rows): a finished hypothesis keeps no tail, but its prompt's
+        cache slot is untouched - the requested rows run their answer tokens and then the latent queries as ONE suffix pass behind that slot
+        (`QwenVLEngine.latents_after`, ops.attention_prefix; no ViT, no prefill, nothing written, repeatable). An answer of more than
+        64 - N_QUERY tokens, an invalid row or other token ids take the re-run path; a pass beyond the buffer rows raises CapacityError."""
         g = getattr(self, "_gen", None)
         if g is not None and g.get("fanned") and output_ids.shape[0] == g["tokens"].shape[0]:
             pl, lens, toks = g["prompt_lens"], g["lens"], g["tokens"]
             sel = list(range(toks.shape[0])) if rows is None else [int(r) for r in rows]
             oc = output_ids.cpu().long()
             nt = toks.shape[1]
-            if sel and all(0 <= r < toks.shape[0] and int(pl[r]) + nt <= oc.shape[1] and torch.equal(oc[r, int(pl[r]):int(pl[r]) + nt], toks[r]) for r in sel):
+            same = sel and all(0 <= r < toks.shape[0] and int(pl[r]) + nt <= oc.shape[1] and torch.equal(oc[r, int(pl[r]):int(pl[r]) + nt], toks[r]) for r in sel)
+            if g.get("path") == "beam":
+                # a finished hypothesis keeps no tail: answer + latent queries run as ONE suffix pass behind the prompt's untouched slot
+                nq = self.qwen.latent_q.shape[0]
+                if same and all(1 <= int(lens[r]) and int(lens[r]) + nq <= ops.ATTN_PREFIX_MAX_ROWS for r in sel):
+                    return self.qwen.latents_after(g["state"], [int(g["prompt_of"][r]) for r in sel], [toks[r, : int(lens[r])].tolist() for r in sel])
+            elif same:
                 return self.qwen.latents_behind(g["state"], sel, [int(toks[r, lens[r] - 1]) for r in sel], [int(pl[r] + lens[r] - 1) for r in sel])
         if rows is not None:
             return self.generate_latents(output_ids, pixel_values, image_grid_thw, cached_image_embeds)[torch.as_tensor(list(rows), dtype=torch.long, device=self.device)]

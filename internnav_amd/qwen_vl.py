@@ -412,6 +412,7 @@ class QwenVLEngine:
         # shared-prompt sampling (prefill(sampling=dict(share_prefix=True))): row-count-sized twins of logits / next_tok / seen / xl / hl / _smp_lp
         # and the per-layer answer tails, allocated by the first such call (`_shared_buffers`)
         self._shared = None
+        self._beam = None        # beam search (prefill(beam=)): the second tail set, the beam tables and the histories, allocated by the first beam call
         # constrained decoding (plan(constraint=)): the rows' automaton states, int32 [2, max_seqs] - step `col` reads row col & 1 and writes the
         # other (ops.automaton_mask_rows needs distinct buffers). Allocated by the first constrained call; the shared-prompt twins carry their own.
         self._cstate = None
@@ -448,6 +449,7 @@ class QwenVLEngine:
         t.layers = [dict(L, kv=torch.empty_like(L["kv"])) for L in self.layers]
         t._side = None
         t._shared = None
+        t._beam = None
         t._cstate = None
         t._kv_reset_tracking()
         return t
@@ -725,7 +727,7 @@ class QwenVLEngine:
         return self.x[: P * m]
 
     def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None, penalty: Optional[float] = None, col: int = 0,
-                     sampling: Optional[dict] = None, src: Optional[torch.Tensor] = None, bufs=None, constraint=None):
+                     sampling: Optional[dict] = None, src: Optional[torch.Tensor] = None, bufs=None, constraint=None, beam: Optional[dict] = None):
         """final RMSNorm + lm_head on ONE row per sequence, greedy argmax on the device. row_in_seq: the same row for every sequence,
         or (ragged batches) rows_idx int32 [B] = absolute row of each sequence's last real token. penalty: the selection runs over the
         repetition-penalised logits of the tokens in `seen` and marks the chosen one (`logits` keeps the raw values).
@@ -740,7 +742,10 @@ class QwenVLEngine:
         launch sequence like `_seen_init`: a captured graph re-initialises on replay; with `src` the B logits rows are masked once and all
         B * K row states start there); col > 0: every row's state advances by the token the previous selection left in next_tok. `logits`
         then holds -inf at the banned entries. HF's order is penalty, prefix constraint, warpers; the penalty is elementwise and keeps
-        -inf, so masking first and penalising inside the unchanged selection kernels gives the same result."""
+        -inf, so masking first and penalising inside the unchanged selection kernels gives the same result.
+        beam (state["beam"], with bufs = the shared-prompt twins): the selection launch becomes ops.beam_topm_rows (log-softmax, the penalty on
+        the log-probabilities over the CURRENT seen set, + running score, the M best per row) followed by ops.beam_step (the prompts'
+        bookkeeping). The constraint's mask reads the states `beam_reorder` gathered by parent (col > 0) and still advances them by next_tok."""
         bf = self if bufs is None else bufs
         if rows_idx is not None:
             ops.gather_rows(self.x[: B * S], bf.xl[:B], src=rows_idx)
@@ -751,14 +756,33 @@ class QwenVLEngine:
             ops.linear_w8(bf.hl[:B], *self.lm_head8, out=bf.logits[:B])
         else:
             ops.linear(bf.hl[:B], self.lm_head, out=bf.logits[:B])     # (152064 columns: one wave per 16-column tile owns all of K)
-        if constraint is not None:
+        if constraint is not None and beam is not None:
+            tb, bm = constraint.to(self.device), self._beam
+            if col == 0:
+                bm.cstate.fill_(constraint.start)             # (every row's state, as on the sampled path: the K rows of a prompt start alike)
+                ops.automaton_mask_rows(bf.logits[:B], tb, bm.cstate[1, :B], None, bm.cstate[0, :B])
+            else:                                                 # cstate[1] = the parents' states, gathered by beam_reorder
+                ops.automaton_mask_rows(bf.logits[:B], tb, bm.cstate[1, :B], bf.next_tok[:B], bm.cstate[0, :B])
+        elif constraint is not None:
             tb, st = constraint.to(self.device), bf._cstate
             if col == 0:
                 st.fill_(constraint.start)
                 ops.automaton_mask_rows(bf.logits[:B], tb, st[0, :B], None, st[1, :B])
             else:
                 ops.automaton_mask_rows(bf.logits[:B], tb, st[col & 1, :B], bf.next_tok[:B], st[(col + 1) & 1, :B])
-        if sampling is not None:
+        if beam is not None:
+            bm = self._beam
+            R = B if src is None else src.numel()
+            M = beam["M"]
+            cs, ct = bm.cand_score[: R * M].view(R, M), bm.cand_tok[: R * M].view(R, M)
+            if col == 0:                                          # HF's start: beam 0 of every prompt at 0, the others at -1e9 (part of the launch sequence)
+                rs = bm.run_score[:R].view(-1, beam["K"])
+                rs.fill_(-1.0e9)
+                rs[:, 0].fill_(0.0)
+            ops.beam_topm_rows(bf.logits[:B], bm.run_score[:R], cs, ct, src=src, seen=None if penalty is None else bm.seen[beam["flip"]],
+                               penalty=1.0 if penalty is None else penalty)
+            ops.beam_step(cs, ct, self._beam_view(beam, R), col, beam["max_new_tokens"], beam["length_penalty"], beam["early_stopping"])
+        elif sampling is not None:
             R = B if src is None else src.numel()
             assert col < sampling["u"].shape[0] and col < bf._smp_lp.shape[0] and R <= sampling["u"].shape[1], (col, R, sampling["u"].shape)
             ops.sample_rows(bf.logits[:B], sampling["u"][col, :R], bf.next_tok[:R], bf._smp_lp[col, :R], temperature=sampling["temperature"],
@@ -856,8 +880,76 @@ class QwenVLEngine:
         i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(self.device)
         pos = np.broadcast_to(np.asarray(state["next_pos"], dtype=np.int64).reshape(1, R), (3, R))
         return dict(B=R, S=1, pos=i32(pos), b0=0, r0=0,
-                    shared=dict(tails=bufs.tails, T=bufs.T, kv_dst=i32(np.arange(R) * bufs.T + t), tail_len=i32(np.full(R, t + 1)),
+                    shared=dict(tails=sh.get("tails", bufs.tails), T=bufs.T, kv_dst=i32(np.arange(R) * bufs.T + t), tail_len=i32(np.full(R, t + 1)),
                                 tile_rows=sh["tile_rows"], tile_slot=sh["tile_slot"], tile_pfx=sh["tile_pfx"], max_pfx=sh["max_pfx"]))
+
+    def _beam_buffers(self, rows: int, T: int) -> SimpleNamespace:
+        """the buffers of the beam path beside the shared-prompt twins (`_shared_buffers(rows, T)`, whose logits / next_tok / xl / hl, seen set and
+        tails are set 0 here): a second tail set and a second seen set (every step re-parents the rows from the current set into the other,
+        ops.beam_reorder, with the layers' base addresses in device tables), the automaton states (what the mask wrote | gathered by parent),
+        the candidate lists, the running scores / parents / token histories and transition scores (ping-pong) and the finished sets.
+        Allocated by the first beam call, again when the twins were regrown; an engine that never takes the path allocates nothing."""
+        sh = self._shared_buffers(rows, T)
+        bm = self._beam
+        if bm is not None and bm.sh is sh:
+            return bm
+        self._beam = bm = None
+        dev, R, Tt = self.device, sh.rows, sh.T
+        z = lambda *shape, dt=torch.int32: torch.zeros(*shape, dtype=dt, device=dev)      # noqa: E731
+        f32 = torch.float32
+        tails2 = [torch.empty_like(t) for t in sh.tails]
+        base = torch.tensor([[t.data_ptr() for t in sh.tails], [t.data_ptr() for t in tails2]], dtype=torch.int64, device=dev)
+        self._beam = SimpleNamespace(
+            sh=sh, tails=[sh.tails, tails2], base=base, seen=[sh.seen, torch.zeros_like(sh.seen)], cstate=z(2, R),
+            cand_score=z(R * ops.BEAM_MAX_CANDIDATES, dt=f32), cand_tok=z(R * ops.BEAM_MAX_CANDIDATES), run_score=z(R, dt=f32), parent=z(R),
+            hist=z(2, R, Tt), ts=z(2, R, Tt, dt=f32), fin_tok=z(R, Tt), fin_ts=z(R, Tt, dt=f32), fin_score=z(R, dt=f32), fin_len=z(R), fin_flag=z(R),
+            heur=z(R), done=z(R))
+        return self._beam
+
+    def _beam_view(self, beam: dict, R: int) -> SimpleNamespace:
+        """the state ops.beam_step works on: the first R rows (R // K prompts) of the beam buffers; next_tok is the twins' (the next pass embeds it)"""
+        bm, K = self._beam, beam["K"]
+        return SimpleNamespace(K=K, eos=beam["eos_t"], run_score=bm.run_score[:R], next_tok=bm.sh.next_tok[:R], parent=bm.parent[:R],
+                               hist=[bm.hist[0, :R], bm.hist[1, :R]], ts=[bm.ts[0, :R], bm.ts[1, :R]], fin_tok=bm.fin_tok[:R], fin_ts=bm.fin_ts[:R],
+                               fin_score=bm.fin_score[:R], fin_len=bm.fin_len[:R], fin_flag=bm.fin_flag[:R], heur=bm.heur[: R // K], done=bm.done[: R // K])
+
+    def _beam_state(self, spec: dict, B: int) -> dict:
+        """validated copy of a beam spec (`prefill`); every capacity error is raised here, before anything is launched"""
+        K, T = int(spec["K"]), int(spec["max_new_tokens"])
+        eos = tuple(int(e) for e in spec.get("eos", ()))
+        lp, early = float(spec.get("length_penalty", 1.0)), spec.get("early_stopping", False)
+        if K < 2 or T < 1 or not np.isfinite(lp) or not any(early is v for v in (False, True)) and early != "never":
+            raise ValueError(f"beam spec: K={K} (>= 2), max_new_tokens={T} (>= 1), length_penalty={lp} (finite), early_stopping={early!r} (False, True, 'never')")
+        if self.hd != 128 or self.nh // self.nkv > ops.ATTN_SHARED_MAX_GROUP:
+            raise ValueError(f"beam search needs head dim 128 and at most {ops.ATTN_SHARED_MAX_GROUP} query heads per KV head (ops.attention_shared), "
+                             f"this model has {self.hd} and {self.nh // self.nkv}")
+        M = max(2, 1 + len(eos)) * K
+        if K > 8 or len(eos) > 3 or M > ops.BEAM_MAX_CANDIDATES or M > self.cfg["vocab"]:
+            raise CapacityError(f"num_beams={K} with {len(eos)} EOS ids: at most 8 beams and 3 EOS ids ({ops.BEAM_MAX_CANDIDATES} candidates per prompt)")
+        if B > self.B_max or B * K > min(SKINNY_GEMM_MAX_ROWS, self.x.shape[0]):
+            raise CapacityError(f"{B} prompts x {K} beams exceed max_seqs={self.B_max} prompts or {min(SKINNY_GEMM_MAX_ROWS, self.x.shape[0])} rows "
+                                "(the single-token passes stay on the weight-streaming kernels)")
+        if T > self.max_decode:
+            raise CapacityError(f"max_new_tokens={T} exceeds the engine's max_decode={self.max_decode}")
+        self._beam_buffers(B * K, T)
+        eos_t = torch.tensor(eos, dtype=torch.int32, device=self.device) if eos else None
+        return dict(K=K, M=M, eos=eos, eos_t=eos_t, max_new_tokens=T, length_penalty=lp, early_stopping=early, flip=0)
+
+    def beam_results(self, state: dict) -> SimpleNamespace:
+        """the finished sets of a beam state after `decode`, on the host, [B, K, ...] best first: tokens int64 [B, K, T], token_scores f32 (the
+        hypotheses' per-token transition scores), scores f32 / lengths int64 / finished bool [B, K], done bool [B], and the running rows' tokens /
+        scores / parents of the last step (what the step-by-step tests read)"""
+        bm, K, R = self._beam, state["beam"]["K"], state["B"]
+        B, n, h = R // K, int(state.get("n_sel", 0)), state.get("n_sel", 0) & 1        # (step j wrote history half 1 - (j & 1))
+        c = lambda t: t.cpu()                                                            # noqa: E731
+        return SimpleNamespace(tokens=c(bm.fin_tok[:R]).long().view(B, K, -1), token_scores=c(bm.fin_ts[:R]).view(B, K, -1), scores=c(bm.fin_score[:R]).view(B, K),
+                               lengths=c(bm.fin_len[:R]).long().view(B, K), finished=c(bm.fin_flag[:R]).bool().view(B, K), done=c(bm.done[:B]).bool(),
+                               heur=c(bm.heur[:B]).bool(), run_tokens=c(bm.hist[h, :R, :n]).long().view(B, K, n), run_token_scores=c(bm.ts[h, :R, :n]).view(B, K, n),
+                               run_scores=c(bm.run_score[:R]).view(B, K), parents=c(bm.parent[:R]).long().view(B, K) - torch.arange(B).view(B, 1) * K)
+
+    def beam_done(self, state: dict) -> torch.Tensor:
+        """bool [B] on the host: which prompts of a beam state are done (the one read `generate` makes per decode chunk)"""
+        return self._beam.done[: state["B"] // state["beam"]["K"]].cpu().bool()
 
     def _constraint_buffers(self, bufs=None):
         """the automaton-state pair of a buffer set (the engine's own, or the shared-prompt twins: a grown set of twins starts without one)"""
@@ -1225,7 +1317,8 @@ class QwenVLEngine:
 
     # ---- eager, stateful API (used by the policy layer: answers have data-dependent lengths)
     def prefill(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor], image_grid_thw, cached_embeds: Optional[list] = None,
-                seq_lens=None, prefix_len: int = 0, repetition_penalty: float = 1.0, sampling: Optional[dict] = None, constraint=None) -> dict:
+                seq_lens=None, prefix_len: int = 0, repetition_penalty: float = 1.0, sampling: Optional[dict] = None, constraint=None,
+                beam: Optional[dict] = None) -> dict:
         """seq_lens [B] (optional): RAGGED batch - input_ids is right-padded to a common length S and sequence b has seq_lens[b] real
         tokens. Causal attention keeps every real position independent of the padding behind it, so the prefill runs on the padded
         rectangle; the first token is read at each sequence's own last position and the decode / latent passes append at per-sequence
@@ -1242,7 +1335,19 @@ class QwenVLEngine:
         place (`_share_out`). The selection runs on row-count-sized twins of the max_seqs-sized buffers (`_shared_buffers`, allocated by the
         first such call). Capacity: B <= max_seqs and B * K <= SKINNY_GEMM_MAX_ROWS, else CapacityError before anything is launched.
         plan() / run_decode (the graph path) stay greedy.
-        constraint: as in `plan` - greedy and sampled decoding alike; each returned sequence keeps an automaton state of its own."""
+        constraint: as in `plan` - greedy and sampled decoding alike; each returned sequence keeps an automaton state of its own.
+        beam (opt-in; None = every launch what it was; not combined with sampling): dict(K = num_beams >= 2, max_new_tokens, eos = the EOS ids,
+        length_penalty = 1.0, early_stopping = False | True | "never") - transformers' beam search on the shared-prompt route: the prompts stay
+        in their B slots, the K hypotheses of prompt b are rows b * K .. b * K + K - 1 with tails of their own, and `decode` runs per step
+        ops.beam_reorder (tails, seen sets and automaton states re-parented into the other set of a pair), the single-token pass, the
+        automaton mask, ops.beam_topm_rows and ops.beam_step - no host round trip between the steps. The repetition penalty acts on the
+        LOG-PROBABILITIES (HF runs its processors behind the log-softmax in beam search; the greedy and sampled paths penalise logits); with
+        a constraint the scores are log-probabilities over the ALLOWED tokens (masked in front of the log-softmax, unlike HF's
+        prefix_allowed_tokens_fn under beams, which masks behind it and does not renormalise). Capacity: B <= max_seqs, B * K <= 64, K <= 8,
+        at most 3 EOS ids, max_new_tokens <= max_decode - CapacityError before anything is launched. Read the result with `beam_results`."""
+        if beam is not None:
+            assert sampling is None, "beam search does not sample (beam sampling is not implemented)"
+            beam = self._beam_state(beam, input_ids.shape[0])
         if sampling is not None:
             sampling = self._sampling_state(sampling, input_ids.shape[0])
         P = self.plan(input_ids, image_grid_thw, cached_embeds=cached_embeds, prefix_len=prefix_len, repetition_penalty=repetition_penalty,
@@ -1253,6 +1358,8 @@ class QwenVLEngine:
         st = self.prefill_state(P, input_ids, image_grid_thw, seq_lens)
         if sampling is not None:
             st["sampling"] = sampling
+        if beam is not None:
+            st["beam"] = beam
         return st
 
     def _sampling_state(self, spec: dict, B: int) -> dict:
@@ -1301,12 +1408,16 @@ class QwenVLEngine:
 
     def decode(self, state: dict, n_steps: int) -> torch.Tensor:
         """n greedy steps after prefill (or after a previous decode); returns int32 [B, n] generated tokens (device). The last
-        returned token is sampled but not yet run through the layers (its K/V are not cached)."""
+        returned token is sampled but not yet run through the layers (its K/V are not cached).
+        A beam state (`prefill(beam=)`): the same convention over the B * K running rows - n selections on the first call, n - 1 on a later
+        one, each later selection behind ops.beam_reorder and one pass; the returned tokens are the running rows' (a hypothesis is read from
+        `beam_results`, never from them). Prompts that are done keep decoding harmlessly; `beam_results(state).done` says when to stop."""
         B, S = state["B"], state["S"]
         Sr = state.get("S_run", S)                                # rows per sequence in x (prompt minus a cached prefix)
         smp = state.get("sampling")                               # None: greedy
-        K = smp["K"] if smp is not None and "cur" not in state else 1      # > 1: this call makes the first draw and fans the batch out
-        share = smp is not None and smp.get("share_prefix", False)         # shared prompts: no fan-out, the twins of the selection buffers
+        beam = state.get("beam")                                  # None: no beam search
+        K = (beam["K"] if beam is not None else smp["K"] if smp is not None else 1) if "cur" not in state else 1      # > 1: this call makes the first draw and fans the batch out
+        share = beam is not None or (smp is not None and smp.get("share_prefix", False))      # shared prompts: no fan-out, the twins of the selection buffers
         bufs = self._shared if share else None
         nt = bufs.next_tok if share else self.next_tok
         out =torch.empty(B * K, n_steps, dtype=torch.int32, device=self.device)
@@ -1318,6 +1429,11 @@ class QwenVLEngine:
         if self.token_logprobs and state.get("n_sel", 1) + n_steps - 1 > self.max_decode:      # before anything is launched
             raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} exceeds the engine's max_decode={self.max_decode} "
                                 "log-probability columns")
+        if beam is not None and state.get("n_sel", 1) + n_steps - 1 > beam["max_new_tokens"]:      # before anything is launched
+            raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} exceeds the beam state's max_new_tokens={beam['max_new_tokens']}")
+        if beam is not None:
+            cst["beam"] = beam
+            assert self._beam is not None and self._beam.sh is bufs, "the beam buffers were regrown by another call: this state cannot be continued"
         if "cur" not in state:
             if pen is not None:
                 self._seen_init(state["plan"])
@@ -1342,6 +1458,9 @@ class QwenVLEngine:
                 self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen, col=0, **kw)
                 state["cur"] = lens.copy()
             state["n_sel"] = 1                                    # selections made so far = answer tokens with a log-probability column
+            if beam is not None:                                  # what `latents_after` continues: the prompts as the prefill left them
+                beam["prompts"] = dict(B=B, next_pos=np.asarray(state["next_pos"]).copy(),
+                                       lens=np.full(B, S, dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64).copy())
             if share:
                 self._share_out(state, K)
                 B, lens = state["B"], state.get("lens")
@@ -1353,6 +1472,13 @@ class QwenVLEngine:
             if j == n_steps - 1:
                 break
             cur = state["cur"]
+            if beam is not None:                                  # the rows of the next pass continue their parents: tails, seen sets, automaton states
+                bm, f, con = self._beam, beam["flip"], "constraint" in cst
+                ops.beam_reorder(bm.parent[:B], bm.base[f], bm.base[1 - f], T=bufs.T, t=int(state["shared"]["tail_len"]), row_bytes=self.kv_w * 2,
+                                 seen_src=None if pen is None else bm.seen[f], seen_dst=None if pen is None else bm.seen[1 - f], next_tok=nt,
+                                 n=self.cfg["vocab"], state_src=bm.cstate[0] if con else None, state_dst=bm.cstate[1] if con else None)
+                beam["flip"] = 1 - f
+                state["shared"]["tails"] = bm.tails[1 - f]
             ops.gather_rows(self.embed, self.x_in, src=nt[:B], rows=B)
             if share:
                 self._layers(self._shared_phase(state))
@@ -1433,6 +1559,34 @@ class QwenVLEngine:
         self._layers(ph)
         out = torch.empty(P, nq, H, dtype=torch.bfloat16, device=self.device)
         ops.norm(self.x[: P * m], self.norm_w, None, eps=1e-6, rms=True, out=out.view(P * nq, H), rows=P * nq, in_map=(nq, m, 1))
+        return out
+
+    def latents_after(self, state: dict, prompt_of, answers) -> torch.Tensor:
+        """N_QUERY latent trajectory queries behind finished hypotheses of a beam state, which keep no tail: pair p runs answers[p] (its answer
+        tokens, EOS included where it ended) and then latent_q as ONE suffix pass behind prompt prompt_of[p] in its cache slot, which beam
+        search never writes (`_suffix_phase`, ops.attention_prefix). Nothing is written: the call can be repeated. -> bf16 [P, N_QUERY, H]
+        through the final RMSNorm. ValueError if an answer + N_QUERY exceeds the rows of a suffix pass, CapacityError if the pass exceeds the
+        engine's buffer rows - both before any launch."""
+        nq, H = self.latent_q.shape[0], self.H
+        pr = state["beam"]["prompts"]
+        prompt_of = np.asarray(prompt_of, dtype=np.int64).reshape(-1)
+        P = prompt_of.size
+        alen = np.asarray([len(a) for a in answers], dtype=np.int64)
+        assert P >= 1 and alen.size == P and int(alen.min()) >= 1 and int(prompt_of.min()) >= 0 and int(prompt_of.max()) < pr["B"]
+        m = int(alen.max()) + nq
+        ph = self._suffix_phase(prompt_of, pr["next_pos"][prompt_of], pr["lens"][prompt_of], alen + nq, m)      # (raises before any launch)
+        toks = np.zeros((P, m), dtype=np.int32)
+        for p, a in enumerate(answers):
+            toks[p, : alen[p]] = np.asarray(a, dtype=np.int32)
+        i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(self.device)      # noqa: E731
+        qrows = (np.arange(P)[:, None] * m + alen[:, None] + np.arange(nq)[None]).reshape(-1)
+        ops.gather_rows(self.embed, self.x_in, src=i32(toks.reshape(-1)), rows=P * m)
+        self.x_in[: P * m].index_copy_(0, torch.from_numpy(qrows).to(self.device), self.latent_q.repeat(P, 1))
+        self._layers(ph)
+        tmp = torch.empty(P * nq, H, dtype=self.x.dtype, device=self.device)
+        ops.gather_rows(self.x[: P * m], tmp, src=i32(qrows))
+        out = torch.empty(P, nq, H, dtype=torch.bfloat16, device=self.device)
+        ops.norm(tmp, self.norm_w, None, eps=1e-6, rms=True, out=out.view(P * nq, H), rows=P * nq)
         return out
 
     # ------------------------------------------------------------------------------------------------ HF-style surface
