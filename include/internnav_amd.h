@@ -616,6 +616,33 @@ int ina_beam_reorder(const int64_t* src_base, const int64_t* dst_base, int32_t n
                      int64_t row_bytes, const uint32_t* seen_src, uint32_t* seen_dst, int32_t ld_words, const int32_t* next_tok, int32_t n,
                      const int32_t* state_src, int32_t* state_dst, void* stream);
 
+/* ---- logit_rules_rows: transformers' logits processors sequence_bias, no_repeat_ngram_size, bad_words_ids, min_length / min_new_tokens,
+ *      forced_eos_token_id, suppress_tokens and begin_suppress_tokens as tables on the device, applied in front of the selection kernels above
+ *      (and behind automaton_mask_rows: the forced 0.0 wins over the automaton's -inf, as HF orders them). One workgroup per row; but for the
+ *      forced fill the vocabulary is not walked. X f32 [rows, ldx] with n live columns, modified IN PLACE at selection step `col` (0 = the first
+ *      answer token). Row r's history is hist[r * ld_hist .. + hist_cap): its prompt's len0[r] real tokens (written by the caller), then its answer.
+ *   1 append   col > 0: hist[r][len0[r] + col - 1] = prev_tok[r] (idempotent). The live history is H = len0[r] + col tokens. A row whose
+ *              len0[r] is outside [0, hist_cap - col] has NO history: nothing is stored and no history rule fires for it.
+ *   2 biases   groups g < n_bias, one per DISTINCT target t = grp_tok[g]: b = grp_base[g]; for s in [grp_ptr[g], grp_ptr[g + 1]) in order, when
+ *              sequence s matches, b += seq_bias[s] (fp32); then X[r][t] += b once. Sequence s holds seq_ids[seq_ptr[s] .. seq_ptr[s + 1]) = its
+ *              L - 1 tokens before the target (1 <= L - 1 <= 31); it matches iff H >= L and the history ends in them.
+ *   3 bans     -inf at: every token that follows an occurrence of the history's last ngram - 1 tokens inside the history (ngram >= 1 and
+ *              H >= ngram; ngram 1: every token of the history); the target of every group g in [n_bias, n_groups) one of whose sequences
+ *              matches; eos_tok[] while col < eos_first[r].
+ *   4 forced   col == forced_col and n_forced > 0: the whole row -inf, then 0.0 at forced_tok[].
+ *   5 static   -inf at ban_tok[] (every step) and at begin_tok[] (col == 0) - behind 4, as HF runs suppress_tokens behind forced_eos_token_id.
+ *  Ids outside [0, n) - in the history, prev_tok or any list - are compared but never used as an index. Entries no rule names are not
+ *  written (a NaN there stays that NaN); columns >= n are never touched; the tables are read-only. No atomics: two launches on the same
+ *  inputs give the same bits. Limits: ngram <= 16, n_seqs <= 1024. rows == 0 launches nothing.
+ *  Refusals (NULL X / hist / len0, prev_tok NULL with col > 0, a positive count with a NULL table, rows outside [0, 65535], n < 1, ldx < n,
+ *  hist_cap < 1, ld_hist < hist_cap, col outside [0, hist_cap], ngram outside [0, 16], n_bias > n_groups, n_seqs > 1024) return non-zero
+ *  before any HIP call. Plain arguments: no struct, no ABI bump. */
+int ina_logit_rules_rows(float* X, int32_t ldx, int32_t rows, int32_t n, int32_t col, int32_t* hist, int32_t ld_hist, int32_t hist_cap, const int32_t* len0,
+                         const int32_t* prev_tok, int32_t ngram, const int32_t* grp_tok, const float* grp_base, const int32_t* grp_ptr, int32_t n_bias,
+                         int32_t n_groups, const int32_t* seq_ptr, const int32_t* seq_ids, const float* seq_bias, int32_t n_seqs, int32_t n_ids,
+                         const int32_t* ban_tok, int32_t n_ban, const int32_t* begin_tok, int32_t n_begin, const int32_t* eos_tok, int32_t n_eos,
+                         const int32_t* eos_first, const int32_t* forced_tok, int32_t n_forced, int32_t forced_col, void* stream);
+
 /* ---- select_traj: per env, rank the S samples by critic value; neg = the k lowest (ascending), pos = the k highest
  *      (descending); trajectories are cumsum_t(sample * scale).  reference: navdp_policy.py:317-320. */
 typedef struct ina_select_args {

@@ -326,6 +326,9 @@ SYMBOLS = {
                                    c_int32, c_void_p, c_void_p, c_void_p]),
     "ina_automaton_mask_rows": (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                           c_void_p]),
+    "ina_logit_rules_rows": (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                       c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                       c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "ina_dit_attention": (C.c_int, [C.POINTER(DitAttnArgs), c_void_p]),
     "ina_resize_u8": (C.c_int, [C.POINTER(ResizeU8Args), c_void_p]),
     "ina_qwen_patchify_u8": (C.c_int, [C.POINTER(QwenPatchifyArgs), c_void_p]),

@@ -89,7 +89,8 @@ class InternVLAN1Agent:
         resize_w/h, width/height (camera), continuous_traj, env_num (engine capacity), repetition_penalty (optional: overrides the
         checkpoint's generation_config.json), ignore_generation_config (optional), token_logprobs (optional, default False: every S2Output then
         carries answer_logprob / answer_min_margin, the log-probability of the decoded answer and its smallest top-2 margin), answer_constraint
-        (optional: a constrain.TokenAutomaton every System-2 answer is decoded under, so it always parses), device_preprocess (optional), device_actions
+        (optional: a constrain.TokenAutomaton every System-2 answer is decoded under, so it always parses), generation_rules (optional: a dict of
+        transformers' logits-processor keys - logit_rules.KEYS - or 'file' for generation_config.json's; the default of every System-2 generate()), device_preprocess (optional), device_actions
         (optional, default False: System-1's trajectories become the step's action table in one kernel launch instead of one numpy
         traj_to_actions per env; `last_action_table` then holds the int32 [n, 4] table of the last System-1 call on the device).
         Tests / bench may pass a built `model` + `processor`, or a `policy_factory() -> InternVLAN1Net`, instead."""

@@ -244,6 +244,16 @@ int ina_automaton_mask_rows(float* X, int32_t ldx, int32_t rows, int32_t n, cons
                                      reinterpret_cast<hipStream_t>(stream));
 }
 
+int ina_logit_rules_rows(float* X, int32_t ldx, int32_t rows, int32_t n, int32_t col, int32_t* hist, int32_t ld_hist, int32_t hist_cap, const int32_t* len0,
+                         const int32_t* prev_tok, int32_t ngram, const int32_t* grp_tok, const float* grp_base, const int32_t* grp_ptr, int32_t n_bias,
+                         int32_t n_groups, const int32_t* seq_ptr, const int32_t* seq_ids, const float* seq_bias, int32_t n_seqs, int32_t n_ids,
+                         const int32_t* ban_tok, int32_t n_ban, const int32_t* begin_tok, int32_t n_begin, const int32_t* eos_tok, int32_t n_eos,
+                         const int32_t* eos_first, const int32_t* forced_tok, int32_t n_forced, int32_t forced_col, void* stream) {
+    return ina_launch_logit_rules(X, ldx, rows, n, col, hist, ld_hist, hist_cap, len0, prev_tok, ngram, grp_tok, grp_base, grp_ptr, n_bias, n_groups, seq_ptr,
+                                  seq_ids, seq_bias, n_seqs, n_ids, ban_tok, n_ban, begin_tok, n_begin, eos_tok, n_eos, eos_first, forced_tok, n_forced,
+                                  forced_col, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ina_logprob_rows(const float* X, int32_t ldx, int32_t rows, int32_t n, uint32_t* seen, int32_t ld_words, float penalty, int32_t mark,
                      const int32_t* target, int32_t* tok, float* logprob, float* margin, void* stream) {
     INA_REQUIRE(X && tok && logprob, "logprob_rows: X, tok and logprob required");

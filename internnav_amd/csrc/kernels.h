@@ -96,6 +96,11 @@ int ina_launch_sample(const float* X, int ldx, int x_rows, int rows, int n, uint
                       hipStream_t stream);                                                                                   // decode_sample.hip
 int ina_launch_automaton_mask(float* X, int ldx, int rows, int n, const uint8_t* token_class, int vocab, const uint32_t* allow, const uint8_t* next,
                               int n_states, const int32_t* state_in, const int32_t* prev_tok, int32_t* state_out, hipStream_t stream);   // decode_constrain.hip
+int ina_launch_logit_rules(float* X, int ldx, int rows, int n, int col, int32_t* hist, int ld_hist, int hist_cap, const int32_t* len0,
+                           const int32_t* prev_tok, int ngram, const int32_t* grp_tok, const float* grp_base, const int32_t* grp_ptr, int n_bias, int n_groups,
+                           const int32_t* seq_ptr, const int32_t* seq_ids, const float* seq_bias, int n_seqs, int n_ids, const int32_t* ban_tok, int n_ban,
+                           const int32_t* begin_tok, int n_begin, const int32_t* eos_tok, int n_eos, const int32_t* eos_first, const int32_t* forced_tok,
+                           int n_forced, int forced_col, hipStream_t stream);                                                 // decode_rules.hip
 int ina_launch_beam_topm(const float* X, int ldx, int x_rows, int rows, int n, const uint32_t* seen, int ld_words, float penalty, const float* run_score,
                          const int32_t* src, int M, float* cand_score, int32_t* cand_tok, hipStream_t stream);                 // decode_beam.hip
 int ina_launch_beam_step(const float* cand_score, const int32_t* cand_tok, int B, int K, int M, int T, int step, int max_new, float lenpow, float hyppow,

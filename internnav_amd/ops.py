@@ -1017,6 +1017,37 @@ def beam_reorder(parent: torch.Tensor, src_base: Optional[torch.Tensor] = None, 
     _lib.check(rc, "beam_reorder")
 
 
+def logit_rules_rows(x: torch.Tensor, tables, col: int, hist: torch.Tensor, len0: torch.Tensor, prev_tok: Optional[torch.Tensor] = None,
+                     eos_first: Optional[torch.Tensor] = None, ld_hist: Optional[int] = None) -> torch.Tensor:
+    """transformers' logits-processor keys in front of a selection launch (and behind automaton_mask_rows): per f32 row r of x (modified IN
+    PLACE) at answer column `col` - append prev_tok[r] to the row's history (col > 0), add the finite sequence biases, store -inf over the
+    n-gram, bad-word, EOS (col < eos_first[r]), suppress and begin-suppress bans, and at the forced column make the row -inf with 0.0 at the
+    forced ids (contract: `ina_logit_rules_rows` in include/internnav_amd.h). tables: what CompiledRules.to(device) returns. hist int32
+    [>= rows, hist_cap] (row stride ld_hist elements, default its own: a larger stride reads every K-th history), len0 int32 [rows] the
+    rows' prompt lengths, prev_tok int32 [rows] (required behind column 0), eos_first int32 [rows] (default: the tables')."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    rows, n = x.shape
+    assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.stride(1) == 1
+    ld = hist.stride(0) if ld_hist is None else int(ld_hist)
+    assert (rows - 1) * ld + hist.shape[1] <= (hist.shape[0] - 1) * hist.stride(0) + hist.shape[1] or rows == 0, (rows, ld, tuple(hist.shape))
+    eos_first = tables.eos_first if eos_first is None else eos_first
+    for t in (len0, prev_tok, eos_first):
+        assert t is None or (t.dtype == torch.int32 and t.numel() == rows and t.is_contiguous()), "len0 / prev_tok / eos_first: contiguous int32 [rows]"
+    assert col == 0 or prev_tok is not None
+    if rows == 0:
+        return x
+    p = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    cnt = lambda t: 0 if t is None else t.numel()         # noqa: E731
+    tb = tables
+    rc = _lib.lib().ina_logit_rules_rows(x.data_ptr(), x.stride(0) if rows > 1 else max(x.stride(0), n), rows, n, int(col), hist.data_ptr(), ld, hist.shape[1],
+                                         len0.data_ptr(), p(prev_tok), tb.ngram, p(tb.grp_tok), p(tb.grp_base), p(tb.grp_ptr), tb.n_bias, tb.n_groups,
+                                         p(tb.seq_ptr), p(tb.seq_ids), p(tb.seq_bias), tb.n_seqs, tb.n_ids, p(tb.ban_tok), cnt(tb.ban_tok), p(tb.begin_tok),
+                                         cnt(tb.begin_tok), p(tb.eos_tok), cnt(tb.eos_tok), p(eos_first), p(tb.forced_tok), cnt(tb.forced_tok),
+                                         tb.forced_col, _stream())
+    _lib.check(rc, "logit_rules_rows")
+    return x
+
+
 def dit_v2t(kv2: torch.Tensor, heads: int, v2t: torch.Tensor) -> torch.Tensor:
     """condition V of a NextDiT block -> the transposed key-permuted image dit_attention consumes.
     kv2 bf16 [envs, Lz, 2, heads, 64] (K | V as produced by the fused kv projection); v2t bf16 [envs, heads, 64, 64]."""

@@ -28,7 +28,7 @@ from typing import Any, Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import ops, synthetic
+from . import logit_rules, ops, synthetic
 from .navdp import NavDPPolicyDAT
 from .nextdit import NextDiTSystem1
 from .qwen_vl import ATTN_WIDE_MIN_ROWS, SKINNY_GEMM_MAX_ROWS, EngineKVCache, QwenVLEngine, eos_ids, kv_reuse_fit, kv_reuse_lengths
@@ -196,16 +196,19 @@ _GEN_REFUSED = {
     "penalty_alpha": lambda v: v is None, "exponential_decay_length_penalty": lambda v: v is None, "renormalize_logits": lambda v: not v}
 
 
-def generation_config_from_hf(raw: Optional[dict], default_eos, ignore: bool = False) -> SimpleNamespace:
+def generation_config_from_hf(raw: Optional[dict], default_eos, ignore: bool = False, rules_from_file: bool = False) -> SimpleNamespace:
     """what `generate(do_sample=False)` honours of a checkpoint's generation_config.json (HF starts from that file and overrides only the
     keys it is passed): `repetition_penalty` (default 1.0) and `eos_token_id` (an int or a list; default: config.json's) -> a namespace with
     repetition_penalty, eos_token_id (tuple) and the raw dict. raw None = no file: penalty 1.0, EOS of config.json.
     Sampling-only keys (do_sample, temperature, top_k, top_p, min_p, typical_p) are ignored by greedy decoding, as HF ignores them under
     do_sample=False; the namespace carries the file's do_sample / temperature / top_k / top_p (None = not set) for generate(do_sample=True)
     (`sampling_spec`, which is also where min_p / typical_p / epsilon_cutoff / eta_cutoff are refused - at generate() time, not here).
-    A key that changes greedy output and is not implemented raises NotImplementedError naming it, unless `ignore`."""
+    A key that changes greedy output and is not implemented raises NotImplementedError naming it, unless `ignore`.
+    rules_from_file (default False: today's refusal; generation_rules="file" of the model sets it): the eight logits-processor keys of
+    `logit_rules.KEYS` are then not refused but returned as `rules` (the keys the file switches on, values as they stand; {} otherwise) -
+    the model's default rule set of generate()."""
     raw = dict(raw or {})
-    bad = sorted(k for k, ok in _GEN_REFUSED.items() if k in raw and not ok(raw[k]))
+    bad = sorted(k for k, ok in _GEN_REFUSED.items() if k in raw and not ok(raw[k]) and not (rules_from_file and k in logit_rules.KEYS))
     if bad and not ignore:
         raise NotImplementedError(
             f"generation_config.json sets {', '.join(f'{k}={raw[k]!r}' for k in bad)}: greedy decoding with these is not implemented, and ignoring "
@@ -216,7 +219,8 @@ def generation_config_from_hf(raw: Optional[dict], default_eos, ignore: bool = F
         raise ValueError(f"generation_config.json: repetition_penalty={raw.get('repetition_penalty')!r} is not a strictly positive float")
     eos = raw.get("eos_token_id")
     # the file's sampling keys as they stand (None = not in the file): read only by generate(do_sample=True) (`sampling_spec`), never by greedy
-    return SimpleNamespace(repetition_penalty=pen, eos_token_id=eos_ids(default_eos if eos is None else eos), raw=raw,
+    rules = {k: raw[k] for k in logit_rules.KEYS if rules_from_file and k in raw and not _GEN_REFUSED[k](raw[k])}
+    return SimpleNamespace(repetition_penalty=pen, eos_token_id=eos_ids(default_eos if eos is None else eos), raw=raw, rules=rules,
                            do_sample=raw.get("do_sample"), temperature=raw.get("temperature"), top_k=raw.get("top_k"), top_p=raw.get("top_p"))
 
 
@@ -405,15 +409,23 @@ class InternVLAN1ForCausalLM:
                  max_s2_seqs: Optional[int] = None, num_history: int = 8, resize_w: int = 384, resize_h: int = 384,
                  cam_w: int = 640, cam_h: int = 480, w8_decode: bool = False, generation_config: Optional[dict] = None,
                  ignore_generation_config: bool = False, token_logprobs: bool = False, max_decode: int = 128,
-                 mx4_decode: bool = False):
-        """Engine capacity defaults to the longest prompt the reference's harness can build for (num_history, resize, camera size):
+                 mx4_decode: bool = False, generation_rules=None):
+        """generation_rules (opt-in; None = none): the model's default logits-processor rules of every generate() - a dict of
+        `logit_rules.KEYS` (sequence_bias, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens, forced_eos_token_id,
+        suppress_tokens, begin_suppress_tokens; validated here), or "file": the values generation_config.json sets, which are otherwise
+        refused at load. generate()'s arguments override them key by key.
+        Engine capacity defaults to the longest prompt the reference's harness can build for (num_history, resize, camera size):
         see `s2_capacity`; exceeding it raises `CapacityError` (never a silent STOP).
         token_logprobs (opt-in): the System-2 engine keeps the log-probability and top-2 margin of every greedy token
         (generate(output_logprobs=True)) for answers of up to max_decode tokens (generate() refuses a larger max_new_tokens on such a model);
         off, the launch sequence is the plain one."""
         self.device = torch.device(device)
         # the checkpoint's generation_config.json (None: no such file): generate() starts from it, as HF's does
-        self.generation_config = generation_config_from_hf(generation_config, qwen_cfg["eos_token_id"], ignore=ignore_generation_config)
+        self.generation_config = generation_config_from_hf(generation_config, qwen_cfg["eos_token_id"], ignore=ignore_generation_config,
+                                                           rules_from_file=generation_rules == "file")
+        if not (generation_rules is None or generation_rules == "file" or isinstance(generation_rules, dict)):
+            raise ValueError(f"generation_rules={generation_rules!r}: None, a dict of {', '.join(logit_rules.KEYS)}, or 'file'")
+        self.generation_rules = logit_rules.normalize(self.generation_config.rules if generation_rules == "file" else generation_rules, qwen_cfg["vocab"])
         if system1 not in ("nextdit_async", "navdp_async", "nextdit", "navdp"):
             # the four System-1 types of generate_traj (internvla_n1.py:359-441): 'nextdit' [+ 'async'] and 'navdp' [+ 'async']
             raise NotImplementedError(f"system1={system1!r}: known types are 'nextdit_async' (DualVLN), 'navdp_async', 'nextdit', 'navdp'")
@@ -462,7 +474,7 @@ class InternVLAN1ForCausalLM:
         device = (device_map or {"": "cuda:0"})[""]
         genj = json.loads((p / "generation_config.json").read_text()) if (p / "generation_config.json").exists() else None
         # only the refusal check, before any weight is read (the EOS default is a placeholder): __init__ builds the namespace the model keeps
-        generation_config_from_hf(genj, 0, ignore=bool(kw.get("ignore_generation_config", False)))
+        generation_config_from_hf(genj, 0, ignore=bool(kw.get("ignore_generation_config", False)), rules_from_file=kw.get("generation_rules") == "file")
         weights = _ShardedCheckpoint(files)
         system1 = cfgj.get("system1", "nextdit_async")
         s1_cfg = None
@@ -497,7 +509,9 @@ class InternVLAN1ForCausalLM:
                  temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  num_return_sequences: Optional[int] = None, generator: Optional[torch.Generator] = None, seed: Optional[int] = None,
                  share_prefix: Optional[bool] = None, constraint=None, num_beams: Optional[int] = None, length_penalty: float = 1.0,
-                 early_stopping=False, **kw):
+                 early_stopping=False, sequence_bias=None, no_repeat_ngram_size: Optional[int] = None, bad_words_ids=None,
+                 min_length: Optional[int] = None, min_new_tokens: Optional[int] = None, forced_eos_token_id=None, suppress_tokens=None,
+                 begin_suppress_tokens=None, **kw):
         """greedy decoding by default (do_sample=False is the only mode the reference uses, internvla_n1_policy.py:169-176). Decodes in chunks of
         `decode_chunk` device-side steps and stops once every sequence has emitted EOS. Sequences are right-filled with EOS.
         repetition_penalty / eos_token_id: None = the checkpoint's generation_config.json (`self.generation_config`; without that file 1.0
@@ -566,7 +580,26 @@ class InternVLAN1ForCausalLM:
         log-softmax, so a score is the log-probability over the allowed tokens, renormalised per step - HF's prefix_allowed_tokens_fn under
         beams masks behind the softmax and does not renormalise; a hypothesis that had to take a banned token stays at -inf and is not valid.
         (2) a generation_config.json that sets num_beams > 1 stays refused at load: the agent's captured plan() / run_decode chain is greedy.
-        Refused (as HF / NotImplementedError naming the key): `beam_spec`."""
+        Refused (as HF / NotImplementedError naming the key): `beam_spec`.
+        sequence_bias, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens, forced_eos_token_id, suppress_tokens,
+        begin_suppress_tokens (opt-in; None = the model's `generation_rules`, without them every launch what it was): transformers' logits
+        processors of these names, in `_get_logits_processor`'s order, compiled per call to tables on the device (`logit_rules.compile_rules`:
+        this call's EOS ids, each row's REAL prompt length, max_new_tokens) and applied by one launch in front of every selection
+        (ops.logit_rules_rows) - greedy, output_logprobs (the log-softmax over the processed scores), do_sample with num_return_sequences /
+        share_prefix (a history per returned sequence), constraint= (forced_eos_token_id wins over the automaton), past_key_values and
+        decode_chunk alike. A row's history is its own prompt tokens (cached prefix and image placeholders included, padding not) + its
+        answer: in a ragged batch that is what a batch-1 HF call on the row sees, where HF on a left-padded batch would count and match the
+        pad tokens too. ValueError as HF's validators raise it (`logit_rules.normalize`); with num_beams > 1 NotImplementedError before
+        anything is launched. score_answers and generate_latents apply no rules."""
+        rule_spec = logit_rules.merge(getattr(self, "generation_rules", None), dict(
+            sequence_bias=sequence_bias, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, min_length=min_length,
+            min_new_tokens=min_new_tokens, forced_eos_token_id=forced_eos_token_id, suppress_tokens=suppress_tokens,
+            begin_suppress_tokens=begin_suppress_tokens))
+        if rule_spec:                                            # (without a key the engine is not even looked at here)
+            rule_spec = logit_rules.normalize(rule_spec, self.qwen.cfg["vocab"])
+        if rule_spec and num_beams is not None and int(num_beams) > 1:
+            raise NotImplementedError(f"generate(num_beams > 1) with logit rules ({', '.join(rule_spec)}): beam search applies HF's processors to "
+                                      "log-probabilities and re-parents the histories; not implemented")
         if constraint is not None and getattr(constraint, "vocab", None) != self.qwen.cfg["vocab"]:
             raise ValueError(f"constraint: an automaton over {getattr(constraint, 'vocab', None)} tokens, this model has {self.qwen.cfg['vocab']}")
         bms = beam_spec(num_beams, num_return_sequences, length_penalty, early_stopping, do_sample, share_prefix, kw)
@@ -615,6 +648,7 @@ class InternVLAN1ForCausalLM:
         if attention_mask is not None:
             am = attention_mask.cpu().long()
             assert bool((am[:, 1:] <= am[:, :-1]).all()), "ragged System-2 batches are right-padded (mask = 1...1 0...0)"
+        rules = logit_rules.compile_rules(rule_spec, self.qwen.cfg["vocab"], eos_all, plens, max_new_tokens) if rule_spec else None
         pl = 0
         self._gen = None                                       # the cache slots (and tails) are rewritten from here on: nothing older may be continued
         self.last_kv_reuse = dict(rows=0, fallbacks=0)
@@ -643,6 +677,7 @@ class InternVLAN1ForCausalLM:
         state = self.qwen.prefill(input_ids, pv, image_grid_thw, cached_embeds=cached_image_embeds, seq_lens=plens if attention_mask is not None else None,
                                   prefix_len=pl, **({} if penalty == 1.0 else {"repetition_penalty": penalty}), **self._sampling_kw(smp, B, max_new_tokens, generator, seed, share_prefix),
                                   **({} if constraint is None else {"constraint": constraint}),
+                                  **({} if rules is None else {"logit_rules": rules}),
                                   **({} if bms is None else {"beam": dict(K=bms.K, max_new_tokens=max_new_tokens, eos=eos_all, length_penalty=bms.length_penalty,
                                                                           early_stopping=bms.early_stopping)}))
         self._prefix_out = {}
@@ -1153,7 +1188,7 @@ class InternVLAN1Net:
     def _load(cls, ms: dict):
         """model + processor for a model_settings dict, loaded once per (checkpoint, device) and shared afterwards."""
         key = (str(ms["model_path"]), str(ms.get("device", "cuda:0")), bool(ms.get("w8_decode", False)), bool(ms.get("ignore_generation_config", False)),
-               bool(ms.get("token_logprobs", False)), bool(ms.get("mx4_decode", False)))
+               bool(ms.get("token_logprobs", False)), bool(ms.get("mx4_decode", False)), repr(ms.get("generation_rules")))
         if key not in cls._shared:
             n_env = int(ms.get("env_num", 1) or 1)
             model = InternVLAN1ForCausalLM.from_pretrained(
@@ -1162,6 +1197,7 @@ class InternVLAN1Net:
                 resize_w=ms.get("resize_w", 384), resize_h=ms.get("resize_h", 384), cam_w=ms.get("width", 640), cam_h=ms.get("height", 480),
                 w8_decode=bool(ms.get("w8_decode", False)),      # System-2 single-token passes on FP8 weights (QwenVLEngine(w8_decode=True))
                 ignore_generation_config=bool(ms.get("ignore_generation_config", False)),
+                generation_rules=ms.get("generation_rules"),     # default logits-processor rules of every System-2 generate() (dict, or "file")
                 mx4_decode=bool(ms.get("mx4_decode", False)),    # ... on MXFP4 weights (QwenVLEngine(mx4_decode=True)); not both
                 token_logprobs=bool(ms.get("token_logprobs", False)))   # per-token log-probabilities of System-2 answers (S2Output.answer_logprob)
             cls._shared[key] = (model.eval(), cls.load_processor(ms["model_path"]))

@@ -416,6 +416,9 @@ class QwenVLEngine:
         # constrained decoding (plan(constraint=)): the rows' automaton states, int32 [2, max_seqs] - step `col` reads row col & 1 and writes the
         # other (ops.automaton_mask_rows needs distinct buffers). Allocated by the first constrained call; the shared-prompt twins carry their own.
         self._cstate = None
+        # logits-processor rules (plan(logit_rules=)): the rows' token histories, int32 [max_seqs, max_seq_len + max_decode] - prompt, then answer
+        # (ops.logit_rules_rows). Allocated by the first call that carries rules; the shared-prompt twins carry their own.
+        self._rhist = None
         if self.token_logprobs:
             self._lp_steps, self._mg_steps = (torch.zeros(self.max_decode, max_seqs, dtype=f32, device=dev) for _ in range(2))
             self.tok_logprob, self.tok_margin = self._lp_steps.t(), self._mg_steps.t()
@@ -451,6 +454,7 @@ class QwenVLEngine:
         t._shared = None
         t._beam = None
         t._cstate = None
+        t._rhist = None
         t._kv_reset_tracking()
         return t
 
@@ -727,7 +731,8 @@ class QwenVLEngine:
         return self.x[: P * m]
 
     def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None, penalty: Optional[float] = None, col: int = 0,
-                     sampling: Optional[dict] = None, src: Optional[torch.Tensor] = None, bufs=None, constraint=None, beam: Optional[dict] = None):
+                     sampling: Optional[dict] = None, src: Optional[torch.Tensor] = None, bufs=None, constraint=None, beam: Optional[dict] = None,
+                     rules: Optional[dict] = None):
         """final RMSNorm + lm_head on ONE row per sequence, greedy argmax on the device. row_in_seq: the same row for every sequence,
         or (ragged batches) rows_idx int32 [B] = absolute row of each sequence's last real token. penalty: the selection runs over the
         repetition-penalised logits of the tokens in `seen` and marks the chosen one (`logits` keeps the raw values).
@@ -745,7 +750,14 @@ class QwenVLEngine:
         -inf, so masking first and penalising inside the unchanged selection kernels gives the same result.
         beam (state["beam"], with bufs = the shared-prompt twins): the selection launch becomes ops.beam_topm_rows (log-softmax, the penalty on
         the log-probabilities over the CURRENT seen set, + running score, the M best per row) followed by ops.beam_step (the prompts'
-        bookkeeping). The constraint's mask reads the states `beam_reorder` gathered by parent (col > 0) and still advances them by next_tok."""
+        bookkeeping). The constraint's mask reads the states `beam_reorder` gathered by parent (col > 0) and still advances them by next_tok.
+        rules (P["rules"] of a plan made with logit_rules=; None = the launch sequence it always was): ONE more launch, ops.logit_rules_rows,
+        BEHIND the automaton mask (HF runs the prefix constraint in front of forced_eos_token_id, whose 0.0 must win) and in front of the
+        selection, so the finite biases are in place before the penalty runs inside the selection kernels - HF's order. col 0: every row's
+        history = its prompt, a strided device copy from the plan's id buffer that is part of the launch sequence like `_seen_init` (a
+        captured graph starts over on replay); with `src` the B logits rows are processed once, on the history of each prompt's first
+        returned row (its K histories are equal there). col > 0: every row appends the token the previous selection left in next_tok.
+        `logits` then holds the rule-processed values."""
         bf = self if bufs is None else bufs
         if rows_idx is not None:
             ops.gather_rows(self.x[: B * S], bf.xl[:B], src=rows_idx)
@@ -770,6 +782,17 @@ class QwenVLEngine:
                 ops.automaton_mask_rows(bf.logits[:B], tb, st[0, :B], None, st[1, :B])
             else:
                 ops.automaton_mask_rows(bf.logits[:B], tb, st[col & 1, :B], bf.next_tok[:B], st[(col + 1) & 1, :B])
+        if rules is not None:
+            tb, hist = rules["tabs"], bf._rhist
+            cap = hist.shape[1]
+            if col == 0:
+                R = B if src is None else src.numel()
+                K, ids = R // B, rules["ids"]
+                hist[:R].view(B, K, cap)[:, :, : ids.shape[1]].copy_(ids[:, None, :])
+                ops.logit_rules_rows(bf.logits[:B], tb, 0, hist[:R], tb.len0, None, tb.eos_first, ld_hist=K * cap)
+            else:
+                l0, first = tb.rows(B // tb.len0.numel())
+                ops.logit_rules_rows(bf.logits[:B], tb, col, hist[:B], l0, bf.next_tok[:B], first)
         if beam is not None:
             bm = self._beam
             R = B if src is None else src.numel()
@@ -848,7 +871,7 @@ class QwenVLEngine:
         self._shared = SimpleNamespace(
             rows=rows, T=T, logits=torch.empty(rows, self.cfg["vocab"], dtype=f32, device=dev), next_tok=torch.empty(rows, dtype=torch.int32, device=dev),
             seen=torch.zeros(rows, self.seen.shape[1], dtype=torch.uint32, device=dev), xl=torch.empty(rows, self.H, dtype=f32, device=dev),
-            hl=torch.empty(rows, self.H, dtype=bf, device=dev), _smp_lp=torch.zeros(T, rows, dtype=f32, device=dev), _cstate=None,
+            hl=torch.empty(rows, self.H, dtype=bf, device=dev), _smp_lp=torch.zeros(T, rows, dtype=f32, device=dev), _cstate=None, _rhist=None,
             tails=[torch.empty(rows * T, self.kv_w, dtype=bf, device=dev) for _ in self.layers])
         return self._shared
 
@@ -958,13 +981,20 @@ class QwenVLEngine:
         if bf._cstate is None or bf._cstate.shape[1] < rows:
             bf._cstate = torch.zeros(2, rows, dtype=torch.int32, device=self.device)
 
+    def _rules_buffers(self, bufs=None):
+        """the history rows of a buffer set (the engine's own, or the shared-prompt twins: a grown set of twins starts without them)"""
+        bf = self if bufs is None else bufs
+        rows = self.B_max if bufs is None else bufs.rows
+        if getattr(bf, "_rhist", None) is None or bf._rhist.shape[0] < rows:
+            bf._rhist = torch.zeros(rows, self.S_max + self.max_decode, dtype=torch.int32, device=self.device)
+
     def _seen_init(self, P: dict):
         """launch in front of a decode's first selection: every sequence's seen set = its whole prompt (cached prefix included)"""
         ops.token_seen_set(self.seen, P["rep_ids"], P["rep_lens"], self.cfg["vocab"])
 
     # ---- plan / run: all host work up front, then a pure launch sequence (hipGraph capturable)
     def plan(self, input_ids, image_grid_thw, n_decode: int = 0, with_latents: bool = False, cached_embeds: Optional[list] = None,
-             prefix_len=0, repetition_penalty: float = 1.0, seq_lens=None, constraint=None) -> dict:
+             prefix_len=0, repetition_penalty: float = 1.0, seq_lens=None, constraint=None, logit_rules=None) -> dict:
         """Host-side plan of one S2 call for B equal-length prompts: embedding / scatter indices, vision plan, position ids and cache
         rows of the prefill, of every decode step and of the latent-query pass (fixed-length answers of n_decode tokens).
         cached_embeds: one entry per image (prompt order over the batch), None = run the vision tower on it, else its merged embeddings
@@ -983,7 +1013,12 @@ class QwenVLEngine:
         lengths; with 1.0 nothing is uploaded and the launch sequence is the plain one.
         constraint (a constrain.TokenAutomaton over this vocabulary; None = unconstrained, nothing allocated, every launch what it was):
         every selection of run_decode / decode runs behind ops.automaton_mask_rows (`_last_logits`). The tables are uploaded and the state
-        buffers allocated HERE, so the launch sequence stays capturable."""
+        buffers allocated HERE, so the launch sequence stays capturable.
+        logit_rules (a logit_rules.CompiledRules made for THIS call - its vocabulary, one prompt length per sequence, max_new_tokens >= n_decode;
+        None = no rules, nothing allocated, every launch what it was): every selection of run_decode / decode runs behind
+        ops.logit_rules_rows (`_last_logits`). The tables and the full ids [B, S] are uploaded and the histories allocated HERE; P["rules_key"]
+        is the rule set's identity (a cache of captured graphs keys on it beside the prompt geometry). ValueError for another vocabulary or
+        other prompt lengths, CapacityError when prompt + answer exceed the history rows (max_seq_len + max_decode tokens)."""
         cfg, dev = self.cfg, self.device
         if constraint is not None:
             if getattr(constraint, "vocab", None) != cfg["vocab"]:
@@ -1023,6 +1058,17 @@ class QwenVLEngine:
             P["rep_lens"] = torch.from_numpy(lens.astype(np.int32)).to(dev)
         if constraint is not None:
             P["constraint"] = constraint
+        if logit_rules is not None:
+            lens = np.full(B, S, dtype=np.int64) if seq_lens is None else np.asarray(seq_lens, dtype=np.int64).reshape(B)
+            if logit_rules.vocab != cfg["vocab"] or logit_rules.len0.tolist() != lens.tolist():
+                raise ValueError(f"logit_rules: compiled for {logit_rules.vocab} tokens and prompt lengths {logit_rules.len0.tolist()}, this call has "
+                                 f"{cfg['vocab']} and {lens.tolist()}")
+            if int(lens.max()) + max(int(n_decode), 1) > self.S_max + self.max_decode:
+                raise CapacityError(f"logit_rules: prompt of {int(lens.max())} tokens + {n_decode} answer tokens exceed the "
+                                    f"{self.S_max + self.max_decode} tokens of a history row (max_seq_len + max_decode)")
+            self._rules_buffers()
+            P["rules"] = dict(tabs=logit_rules.to(dev), ids=P["rep_ids"] if "rep_ids" in P else torch.from_numpy(ids.astype(np.int32)).to(dev))
+            P["rules_key"] = logit_rules.key
         img_pos = np.nonzero(flat == cfg["image_token_id"])[0].astype(np.int32)
         if grids:
             ntok_all = [t * h * w // 4 for t, h, w in grids]
@@ -1167,6 +1213,8 @@ class QwenVLEngine:
             return
         pen = P.get("rep_penalty")
         cst = {} if P.get("constraint") is None else {"constraint": P["constraint"]}
+        if P.get("rules") is not None:
+            cst["rules"] = P["rules"]
         if j0 == 0:
             if pen is not None:
                 self._seen_init(P)                                # part of the launch sequence: a captured decode re-initialises the set on replay
@@ -1318,7 +1366,7 @@ class QwenVLEngine:
     # ---- eager, stateful API (used by the policy layer: answers have data-dependent lengths)
     def prefill(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor], image_grid_thw, cached_embeds: Optional[list] = None,
                 seq_lens=None, prefix_len: int = 0, repetition_penalty: float = 1.0, sampling: Optional[dict] = None, constraint=None,
-                beam: Optional[dict] = None) -> dict:
+                beam: Optional[dict] = None, logit_rules=None) -> dict:
         """seq_lens [B] (optional): RAGGED batch - input_ids is right-padded to a common length S and sequence b has seq_lens[b] real
         tokens. Causal attention keeps every real position independent of the padding behind it, so the prefill runs on the padded
         rectangle; the first token is read at each sequence's own last position and the decode / latent passes append at per-sequence
@@ -1344,16 +1392,25 @@ class QwenVLEngine:
         LOG-PROBABILITIES (HF runs its processors behind the log-softmax in beam search; the greedy and sampled paths penalise logits); with
         a constraint the scores are log-probabilities over the ALLOWED tokens (masked in front of the log-softmax, unlike HF's
         prefix_allowed_tokens_fn under beams, which masks behind it and does not renormalise). Capacity: B <= max_seqs, B * K <= 64, K <= 8,
-        at most 3 EOS ids, max_new_tokens <= max_decode - CapacityError before anything is launched. Read the result with `beam_results`."""
+        at most 3 EOS ids, max_new_tokens <= max_decode - CapacityError before anything is launched. Read the result with `beam_results`.
+        logit_rules: as in `plan` - greedy and sampled decoding alike; each returned sequence keeps a history of its own. With beam= it raises
+        NotImplementedError before anything is launched (HF applies the processors to log-probabilities there, and the histories would have
+        to be re-parented)."""
+        if beam is not None and logit_rules is not None:
+            raise NotImplementedError("beam search (num_beams > 1) with logit rules (sequence_bias, no_repeat_ngram_size, bad_words_ids, min_length, "
+                                      "min_new_tokens, forced_eos_token_id, suppress_tokens, begin_suppress_tokens) is not implemented")
         if beam is not None:
             assert sampling is None, "beam search does not sample (beam sampling is not implemented)"
             beam = self._beam_state(beam, input_ids.shape[0])
         if sampling is not None:
             sampling = self._sampling_state(sampling, input_ids.shape[0])
         P = self.plan(input_ids, image_grid_thw, cached_embeds=cached_embeds, prefix_len=prefix_len, repetition_penalty=repetition_penalty,
-                      seq_lens=seq_lens, **({} if constraint is None else {"constraint": constraint}))
+                      seq_lens=seq_lens, **({} if constraint is None else {"constraint": constraint}),
+                      **({} if logit_rules is None else {"logit_rules": logit_rules}))
         if constraint is not None and sampling is not None and sampling.get("share_prefix"):
             self._constraint_buffers(self._shared)
+        if logit_rules is not None and sampling is not None and sampling.get("share_prefix"):
+            self._rules_buffers(self._shared)
         self.run_prefill(P, pixel_values)
         st = self.prefill_state(P, input_ids, image_grid_thw, seq_lens)
         if sampling is not None:
@@ -1424,6 +1481,12 @@ class QwenVLEngine:
         lens = state.get("lens")
         pen = state["plan"].get("rep_penalty")
         cst = {} if state["plan"].get("constraint") is None else {"constraint": state["plan"]["constraint"]}
+        if state["plan"].get("rules") is not None:
+            cst["rules"] = state["plan"]["rules"]
+            top = int(np.max(state["lens"])) if state.get("lens") is not None else S
+            if top + state.get("n_sel", 1) + n_steps - 1 > self.S_max + self.max_decode:      # before anything is launched
+                raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} behind a prompt of {top} tokens exceeds the "
+                                    f"{self.S_max + self.max_decode} tokens of a history row (max_seq_len + max_decode)")
         if smp is not None and state.get("n_sel", 1) + n_steps - 1 > smp["u"].shape[0]:          # before anything is launched
             raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} exceeds the {smp['u'].shape[0]} rows of the sampling state's uniform table")
         if self.token_logprobs and state.get("n_sel", 1) + n_steps - 1 > self.max_decode:      # before anything is launched
@@ -1591,11 +1654,13 @@ class QwenVLEngine:
 
     # ------------------------------------------------------------------------------------------------ HF-style surface
     def generate(self, input_ids, pixel_values=None, image_grid_thw=None, max_new_tokens: int = 8, eos_token_id=None,
-                 repetition_penalty: float = 1.0, constraint=None, **_):
+                 repetition_penalty: float = 1.0, constraint=None, logit_rules=None, **_):
         """greedy generate: returns sequences int64 [B, S + n] (a row that reached EOS keeps EOS), n = max_new_tokens.
-        eos_token_id: an int or a list (any member ends a row; the row is filled with the first); repetition_penalty and constraint as in `plan`."""
+        eos_token_id: an int or a list (any member ends a row; the row is filled with the first); repetition_penalty, constraint and
+        logit_rules (a CompiledRules for this call) as in `plan`."""
         state = self.prefill(input_ids, pixel_values, image_grid_thw, repetition_penalty=repetition_penalty,
-                             **({} if constraint is None else {"constraint": constraint}))
+                             **({} if constraint is None else {"constraint": constraint}),
+                             **({} if logit_rules is None else {"logit_rules": logit_rules}))
         toks = self.decode(state, max_new_tokens).cpu().long()
         eos_all = eos_ids(self.cfg["eos_token_id"] if eos_token_id is None else eos_token_id)
         eos = eos_all[0]
