@@ -213,9 +213,20 @@ def dropout(x, p, seed, out=None, out_dtype=None, salt=None):
 
 
 def attention_bwd(q, k, v, o, do, scale=None, causal=False, dq=None, dk=None, dv=None, drop_p=0.0, **_):
+    """the function the kernel defines: delta = rowsum(dO * o) of the GIVEN (stored, bf16) o, not of a recomputed one."""
     assert drop_p == 0.0 or COUNT_ONLY
-    qr, kr, vr = (t.float().detach().requires_grad_(True) for t in (q, k, v))
-    gq, gk, gv = torch.autograd.grad(_attn(qr, kr, vr, causal), (qr, kr, vr), do.float())
+    qf, kf, vf, of, dof = (t.float() for t in (q, k, v, o, do))
+    B, Lq, H, D = qf.shape
+    Lk = kf.shape[1]
+    sc = D ** -0.5 if scale is None else scale
+    s = torch.einsum("bqhd,bkhd->bhqk", qf, kf) * sc
+    if causal:
+        s = s.masked_fill(~(torch.arange(Lk)[None, :] <= torch.arange(Lq)[:, None] + (Lk - Lq)), float("-inf"))
+    P = torch.softmax(s, -1)
+    delta = (dof * of).sum(-1).permute(0, 2, 1)[..., None]
+    dS = P * (torch.einsum("bqhd,bkhd->bhqk", dof, vf) - delta) * sc
+    gq, gk = torch.einsum("bhqk,bkhd->bqhd", dS, kf), torch.einsum("bhqk,bqhd->bkhd", dS, qf)
+    gv = torch.einsum("bhqk,bqhd->bkhd", P, dof)
     return _store(dq, gq, BF), _store(dk, gk, BF), _store(dv, gv, BF)
 
 
