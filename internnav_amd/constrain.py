@@ -2,7 +2,7 @@
 
 A System-2 answer is STOP, a run of arrow symbols or two pixel coordinates. A `TokenAutomaton` is a small deterministic automaton over token
 CLASSES that says which tokens may come next; `ops.automaton_mask_rows` consults its tables on the device in front of every selection launch
-(`QwenVLEngine._last_logits(constraint=)`), so a constrained answer is well formed by construction - what HF's prefix_allowed_tokens_fn
+(`s2_select.Selection._mask`), so a constrained answer is well formed by construction - what HF's prefix_allowed_tokens_fn
 does, without a Python callback per row and step, and inside a captured decode graph.
 
 Tables (limits: S <= 256 states, C <= 256 classes):

@@ -4,7 +4,7 @@
 begin_suppress_tokens=)` mean what they mean in transformers (`generation/logits_process.py`, in `_get_logits_processor`'s order). HF runs them
 as Python objects per step; here `normalize` validates the key values, `compile_rules` resolves them against one call (its EOS ids, the rows'
 prompt lengths, max_new_tokens) into flat tables, and `ops.logit_rules_rows` applies the tables in ONE launch in front of every selection
-(`QwenVLEngine._last_logits(rules=)`), inside a captured decode graph as well. The "history" of a row is its own real prompt tokens (cached
+(`s2_select.Selection._rules`), inside a captured decode graph as well. The "history" of a row is its own real prompt tokens (cached
 prefix and image placeholders included, padding not) followed by its answer so far.
 
 Tables of a `CompiledRules` (int32 / float32; limits MAX_SEQUENCES multi-token sequences of at most MAX_SEQUENCE_LEN tokens, n <= MAX_NGRAM):

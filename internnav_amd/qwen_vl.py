@@ -34,6 +34,7 @@ import torch
 
 from . import ops
 from .runtime import CapacityError
+from .s2_select import Selection
 
 
 # ---------------------------------------------------------------------------------------------------- host index logic (integers only)
@@ -159,6 +160,34 @@ def eos_ids(eos) -> Tuple[int, ...]:
     out = tuple(int(e) for e in (eos if isinstance(eos, (list, tuple)) else [eos]))
     assert out, "eos_token_id: an int or a non-empty list"
     return out
+
+
+def _ids_np(input_ids) -> np.ndarray:
+    """token ids (a tensor on any device, or anything array-like) as int64 on the host"""
+    return (input_ids.cpu().numpy() if isinstance(input_ids, torch.Tensor) else np.asarray(input_ids)).astype(np.int64)
+
+
+def _grid_list(image_grid_thw) -> List[Tuple[int, int, int]]:
+    """image_grid_thw (a tensor [n_images, 3], or None for a call without images) as a list of (t, h, w)"""
+    return [tuple(int(v) for v in g) for g in (image_grid_thw.tolist() if image_grid_thw is not None else [])]
+
+
+def _prompt_lens(B: int, S: int, lens) -> np.ndarray:
+    """real tokens per prompt of a batch of B prompts padded to S: lens [B], or None when every prompt fills the rectangle"""
+    return np.full(B, S, dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64).reshape(B)
+
+
+def prompt_images(ids: np.ndarray, ntok: Sequence[int], image_token_id: int):
+    """(sequence, first token, last token) of every image of a batch, in prompt order: image k fills the next ntok[k] image tokens of its sequence"""
+    k = 0
+    for b in range(ids.shape[0]):
+        ipos = np.nonzero(ids[b] == image_token_id)[0]
+        cum = 0
+        while cum < ipos.size:
+            assert k < len(ntok), "image count of the prompts and image_grid_thw disagree"
+            yield b, int(ipos[cum]), int(ipos[cum + ntok[k] - 1])
+            cum += ntok[k]
+            k += 1
 
 
 class EngineKVCache:
@@ -596,6 +625,17 @@ class QwenVLEngine:
             return ops.linear_w8(x, *L[k + "8"], **kw)
         return ops.linear(x, L[k], **kw)
 
+    def _lm_head(self, h: torch.Tensor, out: torch.Tensor):
+        """lm_head on the rows of h: the fp8 weight stream on a w8_decode / mx4_decode engine, like every other weight-streaming GEMM"""
+        if (self.w8_decode or self.mx4_decode) and h.shape[0] <= SKINNY_GEMM_MAX_ROWS:
+            ops.linear_w8(h, *self.lm_head8, out=out)
+        else:
+            ops.linear(h, self.lm_head, out=out)                  # (152064 columns: one wave per 16-column tile owns all of K)
+
+    def _i32(self, v) -> torch.Tensor:
+        """a host-built index table on the device, int32"""
+        return torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(self.device)
+
     # ------------------------------------------------------------------------------------------------ text model
     def _phase(self, B: int, S: int, pos3: np.ndarray, cache_pos0, k_len: Optional[np.ndarray] = None, b0: int = 0) -> dict:
         """host side of one pass of the decoder stack over B x S new tokens: 3-D position ids, cache rows, key lengths.
@@ -694,7 +734,6 @@ class QwenVLEngine:
         (pfx_len[p] cached tokens, next text position next_pos[p]) with suf_len[p] <= m tokens of its own. Positions are next_pos + i on all
         three m-rope axes - what a decode would give the same tokens. tail_row / tail_len (together, optional): between its slot's rows and
         its own tokens pair p also sees the first tail_len[p] rows of row tail_row[p] of the shared-prompt tails (ops.attention_prefix_tail)."""
-        dev = self.device
         slot, pfx_len, suf_len = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (slot, pfx_len, suf_len))
         P = slot.size
         assert P >= 1 and pfx_len.size == P and suf_len.size == P and np.asarray(next_pos).size == P
@@ -705,15 +744,14 @@ class QwenVLEngine:
         assert int(slot.min()) >= 0 and int(slot.max()) < self.B_max and int(pfx_len.min()) >= 0 and int(pfx_len.max()) <= self.S_max
         assert int(suf_len.min()) >= 0 and int(suf_len.max()) <= m
         pos = (np.asarray(next_pos, dtype=np.int64).reshape(-1, 1) + np.arange(m)[None]).reshape(1, P * m)
-        i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(dev)
-        prefix = dict(slot=i32(slot), pfx_len=i32(pfx_len), suf_len=i32(suf_len), max_pfx=int(pfx_len.max()))
+        prefix = dict(slot=self._i32(slot), pfx_len=self._i32(pfx_len), suf_len=self._i32(suf_len), max_pfx=int(pfx_len.max()))
         if tail_row is not None:
             bufs = self._shared
             tail_row, tail_len = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (tail_row, tail_len))
             assert bufs is not None and tail_row.size == P and tail_len.size == P
             assert int(tail_row.min()) >= 0 and int(tail_row.max()) < bufs.rows and int(tail_len.min()) >= 0 and int(tail_len.max()) <= bufs.T
-            prefix["tail"] = dict(tails=bufs.tails, rows=bufs.rows, T=bufs.T, tail_row=i32(tail_row), tail_len=i32(tail_len), max_tail=int(tail_len.max()))
-        return dict(B=P, S=m, pos=i32(np.broadcast_to(pos, (3, P * m))), b0=0, r0=0, prefix=prefix)
+            prefix["tail"] = dict(tails=bufs.tails, rows=bufs.rows, T=bufs.T, tail_row=self._i32(tail_row), tail_len=self._i32(tail_len), max_tail=int(tail_len.max()))
+        return dict(B=P, S=m, pos=self._i32(np.broadcast_to(pos, (3, P * m))), b0=0, r0=0, prefix=prefix)
 
     def suffix_pass(self, state: dict, prompt_of, tokens, suf_len) -> torch.Tensor:
         """teacher-forced continuation of prefilled prompts WITHOUT touching their cache slots: pair p runs tokens[p, :suf_len[p]] (int [P, m],
@@ -723,103 +761,16 @@ class QwenVLEngine:
         P, m = tokens.shape
         prompt_of = np.asarray(prompt_of, dtype=np.int64).reshape(-1)
         assert prompt_of.size == P and int(prompt_of.min()) >= 0 and int(prompt_of.max()) < state["B"]
-        lens = state.get("lens")
-        pl = np.full(state["B"], state["S"], dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64)
+        pl = _prompt_lens(state["B"], state["S"], state.get("lens"))
         ph = self._suffix_phase(prompt_of, np.asarray(state["next_pos"])[prompt_of], pl[prompt_of], suf_len, m)
-        ops.gather_rows(self.embed, self.x_in, src=torch.from_numpy(tokens.reshape(-1).astype(np.int32)).to(self.device), rows=P * m)
+        ops.gather_rows(self.embed, self.x_in, src=self._i32(tokens.reshape(-1)), rows=P * m)
         self._layers(ph)
         return self.x[: P * m]
 
-    def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None, penalty: Optional[float] = None, col: int = 0,
-                     sampling: Optional[dict] = None, src: Optional[torch.Tensor] = None, bufs=None, constraint=None, beam: Optional[dict] = None,
-                     rules: Optional[dict] = None):
-        """final RMSNorm + lm_head on ONE row per sequence, greedy argmax on the device. row_in_seq: the same row for every sequence,
-        or (ragged batches) rows_idx int32 [B] = absolute row of each sequence's last real token. penalty: the selection runs over the
-        repetition-penalised logits of the tokens in `seen` and marks the chosen one (`logits` keeps the raw values).
-        col (token_logprobs engines): the answer position this selection produces = the column of tok_logprob / tok_margin it fills.
-        sampling (state["sampling"]): ops.sample_rows IN PLACE of the argmax / logprob launch - temperature, top-k, top-p and the draw against
-        row `col` of the state's uniform table; the draw's log-probability goes to column col of the sampling buffer. src int32 [B * K]: the
-        output rows (one per returned sequence, with its own seen set) read the B logits rows through it.
-        bufs: the buffer set of the selection - logits, next_tok, seen, xl, hl, _smp_lp; None = the engine's own (sized by max_seqs), else the
-        row-count-sized twins of the shared-prompt path (`_shared_buffers`).
-        constraint (a constrain.TokenAutomaton; None = the launch sequence it always was): ONE more launch in front of the selection,
-        ops.automaton_mask_rows on the logits rows - col 0: every row in the start state (a device fill of the state buffer, part of the
-        launch sequence like `_seen_init`: a captured graph re-initialises on replay; with `src` the B logits rows are masked once and all
-        B * K row states start there); col > 0: every row's state advances by the token the previous selection left in next_tok. `logits`
-        then holds -inf at the banned entries. HF's order is penalty, prefix constraint, warpers; the penalty is elementwise and keeps
-        -inf, so masking first and penalising inside the unchanged selection kernels gives the same result.
-        beam (state["beam"], with bufs = the shared-prompt twins): the selection launch becomes ops.beam_topm_rows (log-softmax, the penalty on
-        the log-probabilities over the CURRENT seen set, + running score, the M best per row) followed by ops.beam_step (the prompts'
-        bookkeeping). The constraint's mask reads the states `beam_reorder` gathered by parent (col > 0) and still advances them by next_tok.
-        rules (P["rules"] of a plan made with logit_rules=; None = the launch sequence it always was): ONE more launch, ops.logit_rules_rows,
-        BEHIND the automaton mask (HF runs the prefix constraint in front of forced_eos_token_id, whose 0.0 must win) and in front of the
-        selection, so the finite biases are in place before the penalty runs inside the selection kernels - HF's order. col 0: every row's
-        history = its prompt, a strided device copy from the plan's id buffer that is part of the launch sequence like `_seen_init` (a
-        captured graph starts over on replay); with `src` the B logits rows are processed once, on the history of each prompt's first
-        returned row (its K histories are equal there). col > 0: every row appends the token the previous selection left in next_tok.
-        `logits` then holds the rule-processed values."""
-        bf = self if bufs is None else bufs
-        if rows_idx is not None:
-            ops.gather_rows(self.x[: B * S], bf.xl[:B], src=rows_idx)
-            ops.norm(bf.xl[:B], self.norm_w, None, eps=1e-6, rms=True, out=bf.hl[:B], rows=B)
-        else:
-            ops.norm(self.x[: B * S], self.norm_w, None, eps=1e-6, rms=True, out=bf.hl[:B], rows=B, in_map=(1, S, row_in_seq))
-        if (self.w8_decode or self.mx4_decode) and B <= SKINNY_GEMM_MAX_ROWS:
-            ops.linear_w8(bf.hl[:B], *self.lm_head8, out=bf.logits[:B])
-        else:
-            ops.linear(bf.hl[:B], self.lm_head, out=bf.logits[:B])     # (152064 columns: one wave per 16-column tile owns all of K)
-        if constraint is not None and beam is not None:
-            tb, bm = constraint.to(self.device), self._beam
-            if col == 0:
-                bm.cstate.fill_(constraint.start)             # (every row's state, as on the sampled path: the K rows of a prompt start alike)
-                ops.automaton_mask_rows(bf.logits[:B], tb, bm.cstate[1, :B], None, bm.cstate[0, :B])
-            else:                                                 # cstate[1] = the parents' states, gathered by beam_reorder
-                ops.automaton_mask_rows(bf.logits[:B], tb, bm.cstate[1, :B], bf.next_tok[:B], bm.cstate[0, :B])
-        elif constraint is not None:
-            tb, st = constraint.to(self.device), bf._cstate
-            if col == 0:
-                st.fill_(constraint.start)
-                ops.automaton_mask_rows(bf.logits[:B], tb, st[0, :B], None, st[1, :B])
-            else:
-                ops.automaton_mask_rows(bf.logits[:B], tb, st[col & 1, :B], bf.next_tok[:B], st[(col + 1) & 1, :B])
-        if rules is not None:
-            tb, hist = rules["tabs"], bf._rhist
-            cap = hist.shape[1]
-            if col == 0:
-                R = B if src is None else src.numel()
-                K, ids = R // B, rules["ids"]
-                hist[:R].view(B, K, cap)[:, :, : ids.shape[1]].copy_(ids[:, None, :])
-                ops.logit_rules_rows(bf.logits[:B], tb, 0, hist[:R], tb.len0, None, tb.eos_first, ld_hist=K * cap)
-            else:
-                l0, first = tb.rows(B // tb.len0.numel())
-                ops.logit_rules_rows(bf.logits[:B], tb, col, hist[:B], l0, bf.next_tok[:B], first)
-        if beam is not None:
-            bm = self._beam
-            R = B if src is None else src.numel()
-            M = beam["M"]
-            cs, ct = bm.cand_score[: R * M].view(R, M), bm.cand_tok[: R * M].view(R, M)
-            if col == 0:                                          # HF's start: beam 0 of every prompt at 0, the others at -1e9 (part of the launch sequence)
-                rs = bm.run_score[:R].view(-1, beam["K"])
-                rs.fill_(-1.0e9)
-                rs[:, 0].fill_(0.0)
-            ops.beam_topm_rows(bf.logits[:B], bm.run_score[:R], cs, ct, src=src, seen=None if penalty is None else bm.seen[beam["flip"]],
-                               penalty=1.0 if penalty is None else penalty)
-            ops.beam_step(cs, ct, self._beam_view(beam, R), col, beam["max_new_tokens"], beam["length_penalty"], beam["early_stopping"])
-        elif sampling is not None:
-            R = B if src is None else src.numel()
-            assert col < sampling["u"].shape[0] and col < bf._smp_lp.shape[0] and R <= sampling["u"].shape[1], (col, R, sampling["u"].shape)
-            ops.sample_rows(bf.logits[:B], sampling["u"][col, :R], bf.next_tok[:R], bf._smp_lp[col, :R], temperature=sampling["temperature"],
-                            top_k=sampling["top_k"], top_p=sampling["top_p"], seen=None if penalty is None else bf.seen,
-                            penalty=1.0 if penalty is None else penalty, mark=penalty is not None, src=src)
-        elif self.token_logprobs:
-            # the same selection (bit-equal ids) + log-softmax at the chosen index and the top-2 margin, in the launch that replaces the argmax
-            assert col < self.max_decode, (col, self.max_decode)     # (plan() / decode() refuse longer answers before anything is launched)
-            ops.logprob_rows(bf.logits[:B], bf.next_tok[:B], self._lp_steps[col, :B], self._mg_steps[col, :B],
-                             seen=None if penalty is None else bf.seen, penalty=1.0 if penalty is None else penalty, mark=penalty is not None)
-        elif penalty is None:
-            ops.argmax_rows(bf.logits[:B], bf.next_tok[:B])
-        else:
-            ops.argmax_penalty_rows(bf.logits[:B], bf.seen, penalty, bf.next_tok[:B], mark=True)
+    def _last_logits(self, B: int, S: int, row_in_seq, rows_idx: Optional[torch.Tensor] = None):
+        """the plain greedy first selection (`s2_select.Selection.first` without options): final RMSNorm + lm_head on ONE row per sequence of
+        x rows B x S, argmax on the device -> next_tok[:B]"""
+        Selection(self, {}).first(B, S, row_in_seq, rows_idx)
 
     def last_logprobs(self, state: dict):
         """(logprob, margin) f32 [B, n] device views: one value per answer token selected so far from `state` (what `prefill` returned and
@@ -836,30 +787,33 @@ class QwenVLEngine:
         """f32 [rows, n] device view: log q of every token drawn so far from a sampling `state` (rows = B * num_return_sequences), the
         log-softmax of HF's processed scores (penalty, temperature, top-k, top-p) at the draw. A view: the next sampling call overwrites it."""
         assert "sampling" in state, "not a sampling state (prefill(..., sampling=...))"
-        lp = self._shared._smp_lp if state["sampling"].get("share_prefix") else self._smp_lp
-        return lp.t()[: state["B"], : int(state.get("n_sel", 0))]
+        return state["select"].bufs._smp_lp.t()[: state["B"], : int(state.get("n_sel", 0))]
+
+    def _replicate(self, state: dict, K: int):
+        """`state` becomes the decode state of B * K rows, prompt-major (HF's repeat_interleave): next_pos / lens / cur replicated"""
+        state["B"] *= K
+        state["next_pos"] = np.repeat(np.asarray(state["next_pos"]), K)
+        if state.get("lens") is not None:
+            state["lens"] = np.repeat(np.asarray(state["lens"], dtype=np.int64), K)
+            state["cur"] = state["lens"].copy()
+        state["fan"] = K
 
     def _fan_out(self, state: dict, K: int):
         """num_return_sequences = K behind ONE prefill: the prompt rows of cache slot b go to slots b * K + c (ina_kv_copy, out to temporary
         tensors and back in - source slots are destinations too: two launches for the whole batch), and `state` becomes the decode state of
-        B * K rows (prompt-major, HF's repeat_interleave): next_pos / lens / cur replicated. The seen rows were replicated in front of the
+        B * K rows (`_replicate`). The seen rows were replicated in front of the
         first draw, which marks them per returned sequence."""
-        B, lens = state["B"], state.get("lens")
-        n = np.full(B, state["S"], dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64)
+        B = state["B"]
+        n = _prompt_lens(B, state["S"], state.get("lens"))
         self._kv_evict({slot: 0 for slot in range(B * K)})
         tmp = [torch.empty(len(self.layers), int(n[b]), self.kv_w, dtype=torch.bfloat16, device=self.device) for b in range(B)]
         self._kv_copy([(tmp[b], b, int(n[b])) for b in range(B)], to_engine=False)
         self._kv_copy([(tmp[b], b * K + c, int(n[b])) for b in range(B) for c in range(K)], to_engine=True)
-        state["B"] = B * K
-        state["next_pos"] = np.repeat(np.asarray(state["next_pos"]), K)
-        if lens is not None:
-            state["lens"] = np.repeat(n, K)
-            state["cur"] = state["lens"].copy()
-        state["fan"] = K
+        self._replicate(state, K)
 
     def _shared_buffers(self, rows: int, T: int) -> SimpleNamespace:
         """the buffers of the shared-prompt sampling path, sized by its ROW count (returned sequences), not by max_seqs: twins of logits /
-        next_tok / seen / xl / hl / _smp_lp (what a selection step touches, `_last_logits(bufs=)`) and per layer a tail [rows * T, 2 * Hkv * hd]
+        next_tok / seen / xl / hl / _smp_lp (what a selection touches, `s2_select.Selection.bufs`) and per layer a tail [rows * T, 2 * Hkv * hd]
         in the cache's row format (row r keeps the k|v of its answer token t at tail row r * T + t). Allocated by the first shared call, grown
         only when a later call needs more rows or a longer answer (T <= max_decode); an engine that never takes the path allocates nothing."""
         sh = self._shared
@@ -877,22 +831,16 @@ class QwenVLEngine:
 
     def _share_out(self, state: dict, K: int):
         """num_return_sequences = K behind ONE prefill WITHOUT a cache slot per returned sequence (sampling spec share_prefix): `state` becomes
-        the decode state of B * K rows (prompt-major, next_pos / lens / cur replicated as `_fan_out` replicates them); row b * K + c keeps
+        the decode state of B * K rows (`_replicate`); row b * K + c keeps
         reading prompt b in cache slot b (pfx_len = the prompt's length) and appends its own answer tokens to its tail (tail_len = 0 here).
         Host work only: the tile table of ops.attention_shared (rows of one prompt share a tile) and its per-tile slot / length."""
-        B, lens = state["B"], state.get("lens")
-        n = np.full(B, state["S"], dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64)
+        B = state["B"]
+        n = _prompt_lens(B, state["S"], state.get("lens"))
         prompt_of = np.repeat(np.arange(B), K)
         tiles, owner = ops.attention_shared_plan(prompt_of, self.nh // self.nkv)
-        i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(self.device)
-        state["shared"] = dict(slot=prompt_of, pfx_len=n[prompt_of], tail_len=0, tile_rows=i32(tiles), tile_slot=i32(owner), tile_pfx=i32(n[owner]),
-                               max_pfx=int(n.max()))
-        state["B"] = B * K
-        state["next_pos"] = np.repeat(np.asarray(state["next_pos"]), K)
-        if lens is not None:
-            state["lens"] = np.repeat(n, K)
-            state["cur"] = state["lens"].copy()
-        state["fan"] = K
+        state["shared"] = dict(slot=prompt_of, pfx_len=n[prompt_of], tail_len=0, tile_rows=self._i32(tiles), tile_slot=self._i32(owner),
+                               tile_pfx=self._i32(n[owner]), max_pfx=int(n.max()))
+        self._replicate(state, K)
 
     def _shared_phase(self, state: dict) -> dict:
         """host side of one single-token pass of the shared-prompt path: every row runs its pending token at text position next_pos, appends
@@ -900,10 +848,9 @@ class QwenVLEngine:
         sh, bufs, R = state["shared"], self._shared, state["B"]
         t = int(sh["tail_len"])
         assert t < bufs.T and R <= bufs.rows, (t, bufs.T, R, bufs.rows)
-        i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(self.device)
         pos = np.broadcast_to(np.asarray(state["next_pos"], dtype=np.int64).reshape(1, R), (3, R))
-        return dict(B=R, S=1, pos=i32(pos), b0=0, r0=0,
-                    shared=dict(tails=sh.get("tails", bufs.tails), T=bufs.T, kv_dst=i32(np.arange(R) * bufs.T + t), tail_len=i32(np.full(R, t + 1)),
+        return dict(B=R, S=1, pos=self._i32(pos), b0=0, r0=0,
+                    shared=dict(tails=sh.get("tails", bufs.tails), T=bufs.T, kv_dst=self._i32(np.arange(R) * bufs.T + t), tail_len=self._i32(np.full(R, t + 1)),
                                 tile_rows=sh["tile_rows"], tile_slot=sh["tile_slot"], tile_pfx=sh["tile_pfx"], max_pfx=sh["max_pfx"]))
 
     def _beam_buffers(self, rows: int, T: int) -> SimpleNamespace:
@@ -974,24 +921,6 @@ class QwenVLEngine:
         """bool [B] on the host: which prompts of a beam state are done (the one read `generate` makes per decode chunk)"""
         return self._beam.done[: state["B"] // state["beam"]["K"]].cpu().bool()
 
-    def _constraint_buffers(self, bufs=None):
-        """the automaton-state pair of a buffer set (the engine's own, or the shared-prompt twins: a grown set of twins starts without one)"""
-        bf = self if bufs is None else bufs
-        rows = self.B_max if bufs is None else bufs.rows
-        if bf._cstate is None or bf._cstate.shape[1] < rows:
-            bf._cstate = torch.zeros(2, rows, dtype=torch.int32, device=self.device)
-
-    def _rules_buffers(self, bufs=None):
-        """the history rows of a buffer set (the engine's own, or the shared-prompt twins: a grown set of twins starts without them)"""
-        bf = self if bufs is None else bufs
-        rows = self.B_max if bufs is None else bufs.rows
-        if getattr(bf, "_rhist", None) is None or bf._rhist.shape[0] < rows:
-            bf._rhist = torch.zeros(rows, self.S_max + self.max_decode, dtype=torch.int32, device=self.device)
-
-    def _seen_init(self, P: dict):
-        """launch in front of a decode's first selection: every sequence's seen set = its whole prompt (cached prefix included)"""
-        ops.token_seen_set(self.seen, P["rep_ids"], P["rep_lens"], self.cfg["vocab"])
-
     # ---- plan / run: all host work up front, then a pure launch sequence (hipGraph capturable)
     def plan(self, input_ids, image_grid_thw, n_decode: int = 0, with_latents: bool = False, cached_embeds: Optional[list] = None,
              prefix_len=0, repetition_penalty: float = 1.0, seq_lens=None, constraint=None, logit_rules=None) -> dict:
@@ -1012,11 +941,11 @@ class QwenVLEngine:
         cache included; seq_lens [B] real tokens of right-padded prompts) plus the answer. The plan then uploads the full ids [B, S] and the
         lengths; with 1.0 nothing is uploaded and the launch sequence is the plain one.
         constraint (a constrain.TokenAutomaton over this vocabulary; None = unconstrained, nothing allocated, every launch what it was):
-        every selection of run_decode / decode runs behind ops.automaton_mask_rows (`_last_logits`). The tables are uploaded and the state
+        every selection of run_decode / decode runs behind ops.automaton_mask_rows (`s2_select.Selection`). The tables are uploaded and the state
         buffers allocated HERE, so the launch sequence stays capturable.
         logit_rules (a logit_rules.CompiledRules made for THIS call - its vocabulary, one prompt length per sequence, max_new_tokens >= n_decode;
         None = no rules, nothing allocated, every launch what it was): every selection of run_decode / decode runs behind
-        ops.logit_rules_rows (`_last_logits`). The tables and the full ids [B, S] are uploaded and the histories allocated HERE; P["rules_key"]
+        ops.logit_rules_rows (`s2_select.Selection`). The tables and the full ids [B, S] are uploaded and the histories allocated HERE; P["rules_key"]
         is the rule set's identity (a cache of captured graphs keys on it beside the prompt geometry). ValueError for another vocabulary or
         other prompt lengths, CapacityError when prompt + answer exceed the history rows (max_seq_len + max_decode tokens)."""
         cfg, dev = self.cfg, self.device
@@ -1024,11 +953,10 @@ class QwenVLEngine:
             if getattr(constraint, "vocab", None) != cfg["vocab"]:
                 raise ValueError(f"constraint: an automaton over {getattr(constraint, 'vocab', None)} tokens, this model has {cfg['vocab']}")
             constraint.to(dev)
-            self._constraint_buffers()
         pen = float(repetition_penalty)
         if not (np.isfinite(pen) and pen > 0.0):
             raise ValueError(f"repetition_penalty={repetition_penalty!r}: HF requires a strictly positive float")
-        ids = (input_ids.cpu().numpy() if isinstance(input_ids, torch.Tensor) else np.asarray(input_ids)).astype(np.int64)
+        ids = _ids_np(input_ids)
         B, S = ids.shape
         if B > self.B_max or S > self.S_max:
             raise CapacityError(f"System-2 batch of {B} x {S} tokens exceeds the engine's max_seqs={self.B_max} / max_seq_len={self.S_max}")
@@ -1040,53 +968,40 @@ class QwenVLEngine:
         # the last real token there (ragged prefixes decode through the eager `decode()`, which carries per-sequence row indices) - ADVICE r3
         assert (n_decode == 0 and not with_latents) or int(pl.min()) == int(pl.max()), \
             f"plan(n_decode={n_decode}, with_latents={with_latents}) needs ONE prefix length for all sequences, got {pl.tolist()}: use prefill() + decode()"
-        grids = [tuple(int(v) for v in g) for g in (image_grid_thw.tolist() if image_grid_thw is not None else [])]
-        grids_all = grids
+        grids = grids_all = _grid_list(image_grid_thw)
         Sr = S - int(pl.min())                                    # tokens per sequence this call runs (rectangle width)
         run = np.zeros((B, Sr), dtype=np.int64)                   # row b = ids[b, pl[b]:] right-padded
         for b in range(B):
             run[b, : S - pl[b]] = ids[b, pl[b]:]
         flat = run.reshape(-1)
-        prefix_len = pl
-        P = dict(B=B, S=S, S_run=Sr, prefix_len=prefix_len, n_decode=n_decode, ids=torch.from_numpy(flat.astype(np.int32)).to(dev), vision=None,
-                 cached=[], fresh_tokens=[])
+        P = dict(B=B, S=S, S_run=Sr, prefix_len=pl, n_decode=n_decode, ids=self._i32(flat), vision=None, cached=[], fresh_tokens=[])
+        lens = _prompt_lens(B, S, seq_lens)
         if pen != 1.0:
-            lens = np.full(B, S, dtype=np.int64) if seq_lens is None else np.asarray(seq_lens, dtype=np.int64).reshape(B)
             assert int(lens.min()) >= 1 and int(lens.max()) <= S
             P["rep_penalty"] = pen
-            P["rep_ids"] = torch.from_numpy(ids.astype(np.int32)).to(dev)
-            P["rep_lens"] = torch.from_numpy(lens.astype(np.int32)).to(dev)
+            P["rep_ids"] = self._i32(ids)
+            P["rep_lens"] = self._i32(lens)
         if constraint is not None:
             P["constraint"] = constraint
         if logit_rules is not None:
-            lens = np.full(B, S, dtype=np.int64) if seq_lens is None else np.asarray(seq_lens, dtype=np.int64).reshape(B)
             if logit_rules.vocab != cfg["vocab"] or logit_rules.len0.tolist() != lens.tolist():
                 raise ValueError(f"logit_rules: compiled for {logit_rules.vocab} tokens and prompt lengths {logit_rules.len0.tolist()}, this call has "
                                  f"{cfg['vocab']} and {lens.tolist()}")
             if int(lens.max()) + max(int(n_decode), 1) > self.S_max + self.max_decode:
                 raise CapacityError(f"logit_rules: prompt of {int(lens.max())} tokens + {n_decode} answer tokens exceed the "
                                     f"{self.S_max + self.max_decode} tokens of a history row (max_seq_len + max_decode)")
-            self._rules_buffers()
-            P["rules"] = dict(tabs=logit_rules.to(dev), ids=P["rep_ids"] if "rep_ids" in P else torch.from_numpy(ids.astype(np.int32)).to(dev))
+            P["rules"] = dict(tabs=logit_rules.to(dev), ids=P["rep_ids"] if "rep_ids" in P else self._i32(ids))
             P["rules_key"] = logit_rules.key
         img_pos = np.nonzero(flat == cfg["image_token_id"])[0].astype(np.int32)
         if grids:
             ntok_all = [t * h * w // 4 for t, h, w in grids]
             # images inside the prefix: their tokens are cached K/V, nothing of them is needed (neither pixels nor embeddings)
-            in_prefix, img_seq, k = [], [], 0
-            for b in range(B):
-                ipos = np.nonzero(ids[b] == cfg["image_token_id"])[0]
-                cum = 0
-                while cum < ipos.size:
-                    assert k < len(grids), "image count of the prompts and image_grid_thw disagree"
-                    first, last = int(ipos[cum]), int(ipos[cum + ntok_all[k] - 1])
-                    assert last < pl[b] or first >= pl[b], "the cached prefix must end on an image boundary"
-                    in_prefix.append(last < pl[b])
-                    img_seq.append(b)
-                    cum += ntok_all[k]
-                    k += 1
-            assert k == len(grids), "image count of the prompts and image_grid_thw disagree"
-            keep = [k for k, ins in enumerate(in_prefix) if not ins]
+            imgs = list(prompt_images(ids, ntok_all, cfg["image_token_id"]))
+            assert len(imgs) == len(grids), "image count of the prompts and image_grid_thw disagree"
+            for b, first, last in imgs:
+                assert last < pl[b] or first >= pl[b], "the cached prefix must end on an image boundary"
+            img_seq = [b for b, _, _ in imgs]
+            keep = [k for k, (b, _, last) in enumerate(imgs) if last >= pl[b]]
             P["images_run"] = keep
             cached_all = list(cached_embeds) if cached_embeds is not None else [None] * len(grids)
             assert len(cached_all) == len(grids)
@@ -1154,6 +1069,7 @@ class QwenVLEngine:
             p = (nxt + (cur - S))[None, :, None] + np.arange(m + nq)[None, None, :]
             P["latents"] = self._phase(B, m + nq, p, cur)
             P["lat_m"] = m
+        P["select"] = Selection(self, P)                          # (allocates the automaton states / histories of a constrained / ruled call)
         return P
 
     def run_prefill(self, P: dict, pixel_values: Optional[torch.Tensor]):
@@ -1211,34 +1127,43 @@ class QwenVLEngine:
         j1 = n if j1 is None else min(j1, n)
         if n == 0 or j0 >= j1:
             return
-        pen = P.get("rep_penalty")
-        cst = {} if P.get("constraint") is None else {"constraint": P["constraint"]}
-        if P.get("rules") is not None:
-            cst["rules"] = P["rules"]
+        sel = P["select"]
         if j0 == 0:
-            if pen is not None:
-                self._seen_init(P)                                # part of the launch sequence: a captured decode re-initialises the set on replay
-            self._last_logits(B, S, S - 1, penalty=pen, col=0, **cst)
+            sel.first(B, S, S - 1)
         for j in range(j0, j1):
-            tokens_out[:, j].copy_(self.next_tok[:B])
-            if j == n - 1:
-                break
-            ops.gather_rows(self.embed, self.x_in, src=self.next_tok[:B], rows=B)
-            self._layers(P["decode"][j])
-            self._last_logits(B, 1, 0, penalty=pen, col=j + 1, **cst)
+            self._decode_step(sel, B, tokens_out[:, j], None if j == n - 1 else lambda: P["decode"][j], j + 1)      # (a callable: `decode` must make its phase inside the step)
+
+    def _decode_step(self, sel: Selection, B: int, out: torch.Tensor, phase, col: int, shared: Optional[dict] = None):
+        """one step of `run_decode` / `decode`: emit the B tokens the last selection chose into `out`, then - unless they are the call's last
+        (phase None) - embed them, run the single-token pass and select answer column `col`. phase: a callable that gives the pass's phase;
+        it is called behind `sel.reparent`, which turns the tails a beam state's phase reads (shared = state["shared"])."""
+        out.copy_(sel.next_tok[:B])
+        if phase is None:
+            return
+        sel.reparent(B, shared)
+        ops.gather_rows(self.embed, self.x_in, src=sel.next_tok[:B], rows=B)
+        self._layers(phase())
+        sel.step(B, col)
+
+    def _latent_pass(self, R: int, m: int, ph: dict, tail: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the N_QUERY latent queries of R rows, each behind m tail rows, as the pass `ph` over R x (m + N_QUERY) rows of x_in; the query
+        rows go through the final RMSNorm -> out bf16 [R, N_QUERY, H]. tail int32 [R * m]: the tail tokens, embedded here (None with
+        m > 0: the caller has placed their embeddings itself)."""
+        nq, H = self.latent_q.shape[0], self.H
+        x3 = self.x_in[: R * (m + nq)].view(R, m + nq, H)
+        if tail is not None:
+            tmp = self.hl[: R * m]
+            ops.gather_rows(self.embed, tmp, src=tail, rows=R * m)
+            x3[:, :m].copy_(tmp.view(R, m, H))
+        x3[:, m:].copy_(self.latent_q.view(1, nq, H).expand(R, nq, H))
+        self._layers(ph)
+        out = torch.empty(R, nq, H, dtype=torch.bfloat16, device=self.device) if out is None else out
+        ops.norm(self.x[: R * (m + nq)], self.norm_w, None, eps=1e-6, rms=True, out=out.view(R * nq, H), rows=R * nq, in_map=(nq, m + nq, m))
+        return out
 
     def run_latents(self, P: dict, out: torch.Tensor):
         """N_QUERY latent queries (behind the last sampled token) against the KV cache -> out bf16 [B, N_QUERY, H]."""
-        B, H, m = P["B"], self.H, P["lat_m"]
-        nq = self.latent_q.shape[0]
-        x3 = self.x_in[: B * (m + nq)].view(B, m + nq, H)
-        if m:
-            tmp = self.hl[:B]
-            ops.gather_rows(self.embed, tmp, src=self.next_tok[:B], rows=B)
-            x3[:, 0].copy_(tmp)
-        x3[:, m:].copy_(self.latent_q.view(1, nq, H).expand(B, nq, H))
-        self._layers(P["latents"])
-        ops.norm(self.x[: B * (m + nq)], self.norm_w, None, eps=1e-6, rms=True, out=out.view(B * nq, H), rows=B * nq, in_map=(nq, m + nq, m))
+        self._latent_pass(P["B"], P["lat_m"], P["latents"], self.next_tok[: P["B"]] if P["lat_m"] else None, out)
 
     def run_s2(self, P: dict, pixel_values, tokens_out: torch.Tensor, latents_out: Optional[torch.Tensor]):
         """whole System-2 call as one launch sequence: ViT + prefill + n_decode greedy tokens (+ latent queries)."""
@@ -1250,18 +1175,10 @@ class QwenVLEngine:
     # ---- prefix-KV reuse: the K/V of a prompt prefix leave / re-enter the batch's cache slots (device copies, no arithmetic)
     def images_in_prefix(self, input_ids, image_grid_thw, prefix_len) -> List[bool]:
         """per image of the batch (prompt order): do all of its tokens lie inside its sequence's cached prefix?"""
-        ids = (input_ids.cpu().numpy() if isinstance(input_ids, torch.Tensor) else np.asarray(input_ids)).astype(np.int64)
+        ids = _ids_np(input_ids)
         pl = np.broadcast_to(np.asarray(prefix_len, dtype=np.int64).reshape(-1), (ids.shape[0],))
-        ntok = [int(t * h * w) // 4 for t, h, w in (image_grid_thw.tolist() if image_grid_thw is not None else [])]
-        out, k = [], 0
-        for b in range(ids.shape[0]):
-            ipos = np.nonzero(ids[b] == self.cfg["image_token_id"])[0]
-            cum = 0
-            while cum < ipos.size:
-                out.append(int(ipos[cum + ntok[k] - 1]) < pl[b])
-                cum += ntok[k]
-                k += 1
-        return out
+        ntok = [t * h * w // 4 for t, h, w in _grid_list(image_grid_thw)]
+        return [last < pl[b] for b, _, last in prompt_images(ids, ntok, self.cfg["image_token_id"])]
 
     def export_prefix_kv(self, seq: int, n_tokens: int) -> torch.Tensor:
         """K/V of the first n_tokens cached tokens of batch slot `seq`, all layers: bf16 [layers, n_tokens, 2 * kv_heads * head_dim]
@@ -1405,12 +1322,9 @@ class QwenVLEngine:
         if sampling is not None:
             sampling = self._sampling_state(sampling, input_ids.shape[0])
         P = self.plan(input_ids, image_grid_thw, cached_embeds=cached_embeds, prefix_len=prefix_len, repetition_penalty=repetition_penalty,
-                      seq_lens=seq_lens, **({} if constraint is None else {"constraint": constraint}),
-                      **({} if logit_rules is None else {"logit_rules": logit_rules}))
-        if constraint is not None and sampling is not None and sampling.get("share_prefix"):
-            self._constraint_buffers(self._shared)
-        if logit_rules is not None and sampling is not None and sampling.get("share_prefix"):
-            self._rules_buffers(self._shared)
+                      seq_lens=seq_lens, constraint=constraint, logit_rules=logit_rules)
+        if sampling is not None or beam is not None:
+            P["select"] = Selection(self, P, sampling, beam)          # (its state buffers, before any launch)
         self.run_prefill(P, pixel_values)
         st = self.prefill_state(P, input_ids, image_grid_thw, seq_lens)
         if sampling is not None:
@@ -1450,15 +1364,13 @@ class QwenVLEngine:
         """the host-side state `prefill` returns for a plan that has been run (decode / latent passes continue from it): a function of the
         prompt GEOMETRY only (lengths, image-token positions), not of the token values - a captured prefill can be replayed on new tokens
         and pixels of the same geometry and continue from a copy of this state (trainer: graphed frozen prefix)."""
-        st = dict(B=P["B"], S=P["S"], S_run=P["S_run"], next_pos=P["next_pos"].copy(), plan=P)
+        st = dict(B=P["B"], S=P["S"], S_run=P["S_run"], next_pos=P["next_pos"].copy(), plan=P, select=P["select"])
         if seq_lens is not None:
             lens = np.asarray(seq_lens, dtype=np.int64)
             assert lens.shape == (P["B"],) and int(lens.max()) <= P["S"] and int(lens.min()) >= 1
             if bool((lens != P["S"]).any()):
                 assert bool((lens > P["prefix_len"]).all()), "every sequence must have tokens behind its cached prefix"
-                ids = (input_ids.cpu().numpy() if isinstance(input_ids, torch.Tensor) else np.asarray(input_ids)).astype(np.int64)
-                grids = [tuple(int(v) for v in g) for g in (image_grid_thw.tolist() if image_grid_thw is not None else [])]
-                pos3, _ = rope_index(ids, grids, self.cfg["image_token_id"], self.cfg["vision_start_id"])
+                pos3, _ = rope_index(_ids_np(input_ids), _grid_list(image_grid_thw), self.cfg["image_token_id"], self.cfg["vision_start_id"])
                 st["next_pos"] = np.asarray([int(pos3[:, b, : lens[b]].max()) + 1 for b in range(P["B"])], dtype=np.int64)
                 st["lens"] = lens
         return st
@@ -1471,88 +1383,41 @@ class QwenVLEngine:
         `beam_results`, never from them). Prompts that are done keep decoding harmlessly; `beam_results(state).done` says when to stop."""
         B, S = state["B"], state["S"]
         Sr = state.get("S_run", S)                                # rows per sequence in x (prompt minus a cached prefix)
-        smp = state.get("sampling")                               # None: greedy
-        beam = state.get("beam")                                  # None: no beam search
-        K = (beam["K"] if beam is not None else smp["K"] if smp is not None else 1) if "cur" not in state else 1      # > 1: this call makes the first draw and fans the batch out
-        share = beam is not None or (smp is not None and smp.get("share_prefix", False))      # shared prompts: no fan-out, the twins of the selection buffers
-        bufs = self._shared if share else None
-        nt = bufs.next_tok if share else self.next_tok
-        out =torch.empty(B * K, n_steps, dtype=torch.int32, device=self.device)
-        lens = state.get("lens")
-        pen = state["plan"].get("rep_penalty")
-        cst = {} if state["plan"].get("constraint") is None else {"constraint": state["plan"]["constraint"]}
-        if state["plan"].get("rules") is not None:
-            cst["rules"] = state["plan"]["rules"]
-            top = int(np.max(state["lens"])) if state.get("lens") is not None else S
-            if top + state.get("n_sel", 1) + n_steps - 1 > self.S_max + self.max_decode:      # before anything is launched
-                raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} behind a prompt of {top} tokens exceeds the "
-                                    f"{self.S_max + self.max_decode} tokens of a history row (max_seq_len + max_decode)")
-        if smp is not None and state.get("n_sel", 1) + n_steps - 1 > smp["u"].shape[0]:          # before anything is launched
-            raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} exceeds the {smp['u'].shape[0]} rows of the sampling state's uniform table")
-        if self.token_logprobs and state.get("n_sel", 1) + n_steps - 1 > self.max_decode:      # before anything is launched
-            raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} exceeds the engine's max_decode={self.max_decode} "
-                                "log-probability columns")
-        if beam is not None and state.get("n_sel", 1) + n_steps - 1 > beam["max_new_tokens"]:      # before anything is launched
-            raise CapacityError(f"answer token {state.get('n_sel', 1) + n_steps - 1} exceeds the beam state's max_new_tokens={beam['max_new_tokens']}")
-        if beam is not None:
-            cst["beam"] = beam
-            assert self._beam is not None and self._beam.sh is bufs, "the beam buffers were regrown by another call: this state cannot be continued"
+        sel = state["select"]
+        n = _prompt_lens(B, S, state.get("lens"))
+        sel.check_chunk(state.get("n_sel", 1) + n_steps - 1, int(n.max()))      # the last answer token of this chunk: refused before anything is launched
+        K = sel.K if "cur" not in state else 1                                 # > 1: this call makes the first draw and fans the batch out
+        out = torch.empty(B * K, n_steps, dtype=torch.int32, device=self.device)
         if "cur" not in state:
-            if pen is not None:
-                self._seen_init(state["plan"])
-            kw = {} if smp is None else {"sampling": smp}
-            kw.update(cst)
-            if share:
-                kw["bufs"] = bufs
-            if K > 1 or share:
-                kw["src"] = torch.arange(B, dtype=torch.int32, device=self.device).repeat_interleave(K)
-                if pen is not None:                               # one seen set per returned sequence: the draw marks row b * K + c
-                    bits = self.seen.view(torch.int32)
-                    (bufs.seen.view(torch.int32) if share else bits)[: B * K].copy_(bits[:B].repeat_interleave(K, dim=0))
-            if lens is None and bool((state["plan"]["prefix_len"] == state["plan"]["prefix_len"][0]).all()):
-                self._last_logits(B, Sr, Sr - 1, penalty=pen, col=0, **kw)
-                state["cur"] = S
-            elif lens is None:       # equal-length prompts behind prefixes of different lengths: each sequence's last real row
-                rows = torch.from_numpy((np.arange(B) * Sr + S - state["plan"]["prefix_len"] - 1).astype(np.int32)).to(self.device)
-                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen, col=0, **kw)
-                state["cur"] = S
+            # each sequence's last real row in its run rectangle: one row index serves all unless the prompts or their prefixes are ragged
+            last = n - state["plan"]["prefix_len"] - 1
+            if bool((last == Sr - 1).all()):
+                sel.first(B, Sr, Sr - 1)
             else:
-                rows = torch.from_numpy((np.arange(B) * Sr + lens - state["plan"]["prefix_len"] - 1).astype(np.int32)).to(self.device)
-                self._last_logits(B, Sr, None, rows_idx=rows, penalty=pen, col=0, **kw)
-                state["cur"] = lens.copy()
+                sel.first(B, Sr, rows_idx=self._i32(np.arange(B) * Sr + last))
+            state["cur"] = S if state.get("lens") is None else n.copy()
             state["n_sel"] = 1                                    # selections made so far = answer tokens with a log-probability column
-            if beam is not None:                                  # what `latents_after` continues: the prompts as the prefill left them
-                beam["prompts"] = dict(B=B, next_pos=np.asarray(state["next_pos"]).copy(),
-                                       lens=np.full(B, S, dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64).copy())
-            if share:
+            if "beam" in state:                                   # what `latents_after` continues: the prompts as the prefill left them
+                state["beam"]["prompts"] = dict(B=B, next_pos=np.asarray(state["next_pos"]).copy(), lens=n.copy())
+            if sel.shared:
                 self._share_out(state, K)
-                B, lens = state["B"], state.get("lens")
             elif K > 1:
                 self._fan_out(state, K)
-                B, lens = state["B"], state.get("lens")
+            B = state["B"]
+        def phase():
+            if sel.shared:
+                return self._shared_phase(state)
+            cur = state["cur"]
+            return self._phase(B, 1, state["next_pos"][None, :, None], cur, k_len=cur + 1 if np.ndim(cur) else None)      # (ragged batch: per-sequence cache positions)
+
         for j in range(n_steps):
-            out[:, j].copy_(nt[:B])
+            self._decode_step(sel, B, out[:, j], None if j == n_steps - 1 else phase, state["n_sel"], state.get("shared"))
             if j == n_steps - 1:
                 break
-            cur = state["cur"]
-            if beam is not None:                                  # the rows of the next pass continue their parents: tails, seen sets, automaton states
-                bm, f, con = self._beam, beam["flip"], "constraint" in cst
-                ops.beam_reorder(bm.parent[:B], bm.base[f], bm.base[1 - f], T=bufs.T, t=int(state["shared"]["tail_len"]), row_bytes=self.kv_w * 2,
-                                 seen_src=None if pen is None else bm.seen[f], seen_dst=None if pen is None else bm.seen[1 - f], next_tok=nt,
-                                 n=self.cfg["vocab"], state_src=bm.cstate[0] if con else None, state_dst=bm.cstate[1] if con else None)
-                beam["flip"] = 1 - f
-                state["shared"]["tails"] = bm.tails[1 - f]
-            ops.gather_rows(self.embed, self.x_in, src=nt[:B], rows=B)
-            if share:
-                self._layers(self._shared_phase(state))
+            if sel.shared:
                 state["shared"]["tail_len"] += 1
-            elif lens is None:
-                self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur))
-            else:
-                self._layers(self._phase(B, 1, state["next_pos"][None, :, None], cur, k_len=cur + 1))
-            self._last_logits(B, 1, 0, penalty=pen, col=state["n_sel"], **({} if smp is None else {"sampling": smp}), **({"bufs": bufs} if share else {}), **cst)
             state["n_sel"] += 1
-            state["cur"] = cur + 1
+            state["cur"] = state["cur"] + 1
             state["next_pos"] = state["next_pos"] + 1
         return out
 
@@ -1561,31 +1426,14 @@ class QwenVLEngine:
         tail_tokens int32 [B, m]: tokens to run in front of the queries because their K/V are not cached yet (the last sampled
         token). seq_lens [B]: number of cached tokens to keep per sequence (prompt + answer up to where it ended); the m + N_QUERY
         new tokens are placed right behind them, K/V cached beyond that point (post-EOS decode steps) are ignored / overwritten."""
-        B, H = state["B"], self.H
-        nq = self.latent_q.shape[0]
+        B, nq = state["B"], self.latent_q.shape[0]
         m = 0 if tail_tokens is None else tail_tokens.shape[1]
-        rows = B * (m + nq)
         cur = state.get("cur", state.get("lens", state["S"]))
-        x3 = self.x_in[:rows].view(B, m + nq, H)
-        if m:
-            tmp = self.hl[: B * m]
-            ops.gather_rows(self.embed, tmp, src=tail_tokens.reshape(-1).contiguous(), rows=B * m)
-            x3[:, :m].copy_(tmp.view(B, m, H))
-        x3[:, m:].copy_(self.latent_q.view(1, nq, H).expand(B, nq, H))
-        if seq_lens is None and np.ndim(cur) > 0:
-            seq_lens = cur                                            # ragged batch: keep everything cached so far, per sequence
-        if seq_lens is None:
-            p = state["next_pos"][None, :, None] + np.arange(m + nq)[None, None, :]
-            ph = self._phase(B, m + nq, p, cur)
-        else:
-            seq_lens = np.asarray(seq_lens, dtype=np.int64)
-            start_pos = state["next_pos"] - (cur - seq_lens)          # text positions advance by one per cached token
-            p = start_pos[None, :, None] + np.arange(m + nq)[None, None, :]
-            ph = self._phase(B, m + nq, p, seq_lens, k_len=seq_lens + m + nq)
-        self._layers(ph)
-        out = torch.empty(B, nq, H, dtype=torch.bfloat16, device=self.device)
-        ops.norm(self.x[:rows], self.norm_w, None, eps=1e-6, rms=True, out=out.view(B * nq, H), rows=B * nq, in_map=(nq, m + nq, m))
-        return out
+        keep = cur if seq_lens is None else np.asarray(seq_lens, dtype=np.int64)      # (ragged batch: everything cached so far, per sequence)
+        start_pos = state["next_pos"] - (cur - keep)                  # text positions advance by one per cached token
+        p = start_pos[None, :, None] + np.arange(m + nq)[None, None, :]
+        ph = self._phase(B, m + nq, p, keep, k_len=None if np.ndim(keep) == 0 else keep + m + nq)
+        return self._latent_pass(B, m, ph, tail_tokens.reshape(-1).contiguous() if m else None)
 
     def latents_behind(self, state: dict, rows, last_tokens, keep_len) -> torch.Tensor:
         """N_QUERY latent trajectory queries behind SELECTED rows of a sampling state (`prefill(sampling=)` + `decode`), without re-running
@@ -1597,8 +1445,7 @@ class QwenVLEngine:
           shared-prompt state   slot = the row's prompt, pfx_len = the prompt's length, tail row = the row, tail_len = keep_len - prompt length;
           one slot per row      slot = the row, pfx_len = keep_len, no tail (fan-out, or one returned sequence per prompt).
         -> bf16 [P, N_QUERY, H] through the final RMSNorm. CapacityError before any launch if P * (1 + N_QUERY) exceeds the buffer rows."""
-        nq, H = self.latent_q.shape[0], self.H
-        m = 1 + nq
+        m = 1 + self.latent_q.shape[0]
         rows, keep = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (rows, keep_len))
         last = np.asarray(last_tokens.cpu() if isinstance(last_tokens, torch.Tensor) else last_tokens, dtype=np.int64).reshape(-1)
         P = rows.size
@@ -1616,13 +1463,8 @@ class QwenVLEngine:
         else:
             assert bool((keep >= 1).all()) and bool((keep <= cur).all()), "keep_len outside what the rows' cache slots hold"
             ph = self._suffix_phase(rows, start, keep, np.full(P, m), m)
-        i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(self.device)
-        ops.gather_rows(self.embed, self.x_in, src=i32(last), dst=i32(np.arange(P) * m), rows=P)
-        self.x_in[: P * m].view(P, m, H)[:, 1:].copy_(self.latent_q.view(1, nq, H).expand(P, nq, H))
-        self._layers(ph)
-        out = torch.empty(P, nq, H, dtype=torch.bfloat16, device=self.device)
-        ops.norm(self.x[: P * m], self.norm_w, None, eps=1e-6, rms=True, out=out.view(P * nq, H), rows=P * nq, in_map=(nq, m, 1))
-        return out
+        ops.gather_rows(self.embed, self.x_in, src=self._i32(last), dst=self._i32(np.arange(P) * m), rows=P)      # straight to each pair's tail row
+        return self._latent_pass(P, 1, ph)
 
     def latents_after(self, state: dict, prompt_of, answers) -> torch.Tensor:
         """N_QUERY latent trajectory queries behind finished hypotheses of a beam state, which keep no tail: pair p runs answers[p] (its answer
@@ -1641,13 +1483,12 @@ class QwenVLEngine:
         toks = np.zeros((P, m), dtype=np.int32)
         for p, a in enumerate(answers):
             toks[p, : alen[p]] = np.asarray(a, dtype=np.int32)
-        i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).to(self.device)      # noqa: E731
         qrows = (np.arange(P)[:, None] * m + alen[:, None] + np.arange(nq)[None]).reshape(-1)
-        ops.gather_rows(self.embed, self.x_in, src=i32(toks.reshape(-1)), rows=P * m)
+        ops.gather_rows(self.embed, self.x_in, src=self._i32(toks.reshape(-1)), rows=P * m)
         self.x_in[: P * m].index_copy_(0, torch.from_numpy(qrows).to(self.device), self.latent_q.repeat(P, 1))
         self._layers(ph)
         tmp = torch.empty(P * nq, H, dtype=self.x.dtype, device=self.device)
-        ops.gather_rows(self.x[: P * m], tmp, src=i32(qrows))
+        ops.gather_rows(self.x[: P * m], tmp, src=self._i32(qrows))
         out = torch.empty(P, nq, H, dtype=torch.bfloat16, device=self.device)
         ops.norm(tmp, self.norm_w, None, eps=1e-6, rms=True, out=out.view(P * nq, H), rows=P * nq)
         return out
@@ -1658,9 +1499,8 @@ class QwenVLEngine:
         """greedy generate: returns sequences int64 [B, S + n] (a row that reached EOS keeps EOS), n = max_new_tokens.
         eos_token_id: an int or a list (any member ends a row; the row is filled with the first); repetition_penalty, constraint and
         logit_rules (a CompiledRules for this call) as in `plan`."""
-        state = self.prefill(input_ids, pixel_values, image_grid_thw, repetition_penalty=repetition_penalty,
-                             **({} if constraint is None else {"constraint": constraint}),
-                             **({} if logit_rules is None else {"logit_rules": logit_rules}))
+        state = self.prefill(input_ids, pixel_values, image_grid_thw, repetition_penalty=repetition_penalty, constraint=constraint,
+                             logit_rules=logit_rules)
         toks = self.decode(state, max_new_tokens).cpu().long()
         eos_all = eos_ids(self.cfg["eos_token_id"] if eos_token_id is None else eos_token_id)
         eos = eos_all[0]
