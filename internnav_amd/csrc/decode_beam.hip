@@ -15,73 +15,56 @@
 //                    state'[r] = state[parent[r]]. A parent outside [0, rows) copies nothing for its row.
 // No atomics anywhere: two launches on the same inputs give the same bits. No workspace.
 //
-// beam_topm_rows, one workgroup of 1024 threads per row, three walks over the row (the second and third come out of the L2):
+// beam_topm_rows, one workgroup of 1024 threads per row, three walks over the row (the second and third come out of the L2; order, penalty
+// and selection order are those of vocab_row.h):
 //   1. the maximum (exact)       2. s = sum expf(x - max)      3. every thread keeps the two best acc of its own entries
 // then M rounds: the best head of the 1024 threads (wave butterfly, 16 wave slots in LDS, one barrier per round) is the next candidate; its
 // owner moves its second entry up, and once both are gone walks its own ~150 entries again for the next two behind the candidate just
 // emitted (rare: a thread that owns three of a row's best M; rows of ties or of -inf, whose best ids lie side by side, take it every round).
 // Summation shape (mirrored by the bound model of tests/beam_ref.py; change both together):
-//   BEAM_THREADS = 1024; aligned rows in 16-byte vectors: thread t takes vectors t, t + 1024, ... and adds their terms in ascending index; rows
-//   whose base is not 16-byte aligned, and the n % 4 tail, one logit per step. A wave's 64 sums: 6-level butterfly; the 16 wave sums: added in
-//   order. expf / logf of the device library (not the fast intrinsics). y = (x - max) - logf(s), the penalty one multiplication or IEEE
-//   division, acc = y + run_score: one rounding each, contraction off - an entry's acc has the same bits whichever walk computes it.
+//   BEAM_THREADS = 1024 (VR_THREADS); a thread adds the terms of its entries in the order of vr_walk (vocab_row.h): 16-byte vectors of an
+//   aligned row, then one logit per step. A wave's 64 sums: 6-level butterfly; the 16 wave sums: added in order. expf / logf of the device
+//   library (not the fast intrinsics). y = (x - max) - logf(s), the penalty one multiplication or IEEE division, acc = y + run_score: one
+//   rounding each, contraction off - an entry's acc has the same bits whichever walk computes it.
 #include <math.h>
 
 #include <algorithm>
 
 #include "common.h"
 #include "kernels.h"
+#include "vocab_row.h"
 
 namespace {
 
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / INA_WAVE;
-constexpr int kUnroll = 4;           // 16-byte logit loads (and their bitmap words) in flight per thread, as in logprob_rows
+constexpr int kThreads = VR_THREADS;
+constexpr int kWaves = VR_WAVES;
 constexpr int kMaxM = 32;
 constexpr int kMaxK = 8;
 constexpr int kNone = 0x7fffffff;    // id of an empty slot: behind every real entry of the same value
 constexpr float kSent = -1.0e9f;     // HF's sentinel
 
-// value descending, id ascending
-__device__ __forceinline__ bool before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
-
 __device__ __forceinline__ float clean(float v) { return v != v ? -INFINITY : v; }
 
-// One walk over the row: f(index, logit, seen bit) for this thread's entries, in ascending index
+// One walk over the row (vocab_row.h): f(index, logit, seen bit) for this thread's entries, in ascending index. f keeps its results in captured
+// variables, the walk carries no state: with scan_top2's candidates carried by value the kernel measured 59.4 against 56.5 us (M = 4)
+struct NoState {};
 template <bool kSeen, typename F>
 __device__ __forceinline__ void for_entries(const float* __restrict__ x, int n, const uint32_t* __restrict__ sr, F f) {
-    const int n4 = ((reinterpret_cast<uintptr_t>(x) & 15) == 0) ? (n >> 2) : 0;
-    int j = threadIdx.x;
-    for (; j + (kUnroll - 1) * kThreads < n4; j += kUnroll * kThreads) {
-        f32x4 v[kUnroll];
-        uint32_t w[kUnroll];
+    vr_walk<VR_UNROLL, kSeen>(
+        x, n, sr, NoState{},
+        [&](NoState st, int j, f32x4 v, uint32_t b) {
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            v[u] = *reinterpret_cast<const f32x4*>(x + 4 * (j + u * kThreads));
-            w[u] = kSeen ? sr[(j + u * kThreads) >> 3] : 0u;      // the four logits of a vector share one bitmap word
-        }
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const int jj = j + u * kThreads;
-            const uint32_t b = (w[u] >> ((4 * jj) & 31)) & 15u;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) f(4 * jj + q, v[u][q], kSeen && ((b >> q) & 1u));
-        }
-    }
-    for (; j < n4; j += kThreads) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * j);
-        const uint32_t b = kSeen ? (sr[j >> 3] >> ((4 * j) & 31)) & 15u : 0u;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) f(4 * j + q, v[q], kSeen && ((b >> q) & 1u));
-    }
-    for (int i = n4 * 4 + threadIdx.x; i < n; i += kThreads) f(i, x[i], kSeen && ((sr[i >> 5] >> (i & 31)) & 1u));
+            for (int q = 0; q < 4; ++q) f(4 * j + q, v[q], (b >> q) & 1u);
+            return st;
+        },
+        [&](NoState st, int i, float v, bool seen_i) { f(i, v, seen_i); return st; });
 }
 
 // acc of one entry (x already clean): the same bits in every walk
 __device__ __forceinline__ float acc_of(float x, bool seen, float mx, float ls, float penalty, float run) {
 #pragma clang fp contract(off)
     float y = mx > -INFINITY ? (x - mx) - ls : -INFINITY;
-    if (seen) y = y < 0.f ? y * penalty : y / penalty;
+    if (seen) y = penalised(y, penalty);
     const float a = y + run;
     return a != a ? -INFINITY : a;
 }
@@ -101,9 +84,9 @@ __device__ __forceinline__ int scan_top2(const float* __restrict__ x, int n, con
     for_entries<kSeen>(x, n, sr, [&](int i, float v, bool s) {
         const float a = acc_of(clean(v), s, mx, ls, penalty, run);
         ++own;
-        if (bounded && !before(bv, bi, a, i)) return;
-        if (before(a, i, e1.v, e1.i)) { e2 = e1; e1 = {a, i}; }
-        else if (before(a, i, e2.v, e2.i)) e2 = {a, i};
+        if (bounded && !vr_before(bv, bi, a, i)) return;
+        if (vr_before(a, i, e1.v, e1.i)) { e2 = e1; e1 = {a, i}; }
+        else if (vr_before(a, i, e2.v, e2.i)) e2 = {a, i};
     });
     return own;
 }
@@ -157,14 +140,14 @@ __global__ __launch_bounds__(kThreads) void beam_topm_kernel(const float* __rest
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(v, o);
             const int oi = __shfl_xor(i, o);
-            if (before(ov, oi, v, i)) { v = ov; i = oi; }
+            if (vr_before(ov, oi, v, i)) { v = ov; i = oi; }
         }
         if (lane == 0) { wv[k & 1][wave] = v; wi[k & 1][wave] = i; }
         __syncthreads();                                          // (slot set k & 1 is written again two barriers from here)
         v = wv[k & 1][0];
         i = wi[k & 1][0];
         for (int w = 1; w < kWaves; ++w)
-            if (before(wv[k & 1][w], wi[k & 1][w], v, i)) { v = wv[k & 1][w]; i = wi[k & 1][w]; }
+            if (vr_before(wv[k & 1][w], wi[k & 1][w], v, i)) { v = wv[k & 1][w]; i = wi[k & 1][w]; }
         if (threadIdx.x == 0) { cand_score[(size_t)r * M + k] = v; cand_tok[(size_t)r * M + k] = i == kNone ? 0 : i; }
         if (i != kNone && e1.i == i) {                            // the owner: ids are unique
             ++popped;

@@ -1,22 +1,21 @@
 // Per-token log-probability of System-2 decoding (gfx950): log-softmax of a vocabulary row at ONE index, fused with the selection the greedy
 // chain already runs (argmax_rows, rope.hip / argmax_penalty_rows, decode_penalty.hip) - what HF returns through
 // generate(output_scores=True) + compute_transition_scores(normalize_logits=True), without a [B, vocab] tensor leaving the device.
-//   logprob_rows   per row r, with y = x or the repetition-penalised row (penalised() of decode_penalty.hip over the bits of `seen`):
+//   logprob_rows   per row r, with y = x or the repetition-penalised row (penalised() of vocab_row.h over the bits of `seen`):
 //                  tok     = target[r], or (target == NULL) the selection of argmax_rows over y - the same total order (value descending,
 //                            index ascending, NaN never greater), so the ids are bit-equal to those kernels whatever the reduction shape
 //                  logprob = y[tok] - max(y) - log sum exp(y - max(y))        (fp32; torch.log_softmax(y, -1)[tok])
 //                  margin  = y[tok] - max of y over the OTHER indices          (the "top-2 margin"; >= 0 when tok was selected)
-// X is only read. One workgroup per row, as in argmax_penalty_rows: the row's bitmap has ONE writer (mark), no global atomics.
+// X is only read. One workgroup per row, walked as vocab_row.h lays out: the row's bitmap has ONE writer (mark), no global atomics.
 //
 // Math: expf / logf of the device library (NOT the __expf / __logf fast intrinsics); the bound model of tests/logprob_ref.py assumes 2 ulp.
 // One pass, online: a thread keeps (best, idx, second, sum) with sum = sum exp(y - best) over what it has seen; when a 16-byte vector raises
 // best the sum is rescaled ONCE by expf(old - new) before the vector's four terms are added.
 //
 // Summation shape (mirrored by tests/logprob_ref.py; change both together):
-//   LOGPROB_THREADS = 1024         threads of a row's workgroup
-//   LOGPROB_VEC = 4                logits per 16-byte vector; aligned rows: thread t takes vectors t, t + 1024, ...; its terms are added
-//                                  sequentially in ascending index, at most one rescale per vector. Rows whose base is not 16-byte aligned
-//                                  (and the n % 4 tail): one logit per step, thread t takes t, t + 1024, ..., at most one rescale per logit
+//   LOGPROB_THREADS = 1024         threads of a row's workgroup (VR_THREADS)
+//   LOGPROB_VEC = 4                logits per 16-byte vector; a thread's terms are added sequentially in the order of vr_walk (vocab_row.h):
+//                                  at most one rescale per vector (acc4), per logit on the one-by-one path (acc1)
 //   LOGPROB_WAVE = 64              a wave's 64 sums are scaled once to the wave's maximum, then added in a 6-level butterfly
 //   LOGPROB_WAVES = 16             the 16 wave sums are scaled once to the row's maximum and added sequentially by thread 0
 // Conventions: a NaN anywhere in the row -> NaN logprob; -inf entries contribute 0; an all -inf row -> tok 0 (selection), NaN logprob.
@@ -24,12 +23,12 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "vocab_row.h"
 
 namespace {
 
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / INA_WAVE;
-constexpr int kUnroll = 4;           // 16-byte logit loads (and their bitmap words) in flight per thread, as in argmax_penalty_rows
+constexpr int kThreads = VR_THREADS;
+constexpr int kWaves = VR_WAVES;
 
 struct Run {
     float best;      // largest y so far (never NaN)
@@ -37,8 +36,6 @@ struct Run {
     float second;    // largest y at any other index
     float sum;       // sum exp(y - best) over every y so far: NaN once a NaN was met, 0 while best is -inf
 };
-
-__device__ __forceinline__ float penalised(float x, float penalty) { return x < 0.f ? x * penalty : x / penalty; }   // IEEE fp32 division
 
 // exp(m - M) for two maxima m <= M; equal maxima (both -inf included) scale by exactly 1, a sum that belongs to m = -inf is 0 or NaN and stays so
 __device__ __forceinline__ float scale_to(float m, float M) { return m == M ? 1.f : expf(m - M); }
@@ -57,16 +54,9 @@ __device__ __forceinline__ void rescale(float m, Run& t) {
 // -inf - (-inf) never appears
 __device__ __forceinline__ float ref_point(float best) { return best > -INFINITY ? best : 0.f; }
 
-template <bool kSeen>
-__device__ __forceinline__ void acc4(f32x4 v, uint32_t w, int j, float penalty, Run& t) {
-    if (kSeen) {
-        const uint32_t b = (w >> ((4 * j) & 31)) & 15u;      // the four logits of a vector share one bitmap word
-        if (b) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if ((b >> q) & 1u) v[q] = penalised(v[q], penalty);
-        }
-    }
+// one 16-byte vector of logits (index 4j .. 4j + 3) and its four seen bits: at most one rescale
+__device__ __forceinline__ void acc4(f32x4 v, uint32_t b, int j, float penalty, Run& t) {
+    vr_penalise4(v, b, penalty);
     const float m = t.best;
 #pragma unroll
     for (int q = 0; q < 4; ++q) take(v[q], 4 * j + q, t);    // ascending index: the first maximum is kept
@@ -76,8 +66,13 @@ __device__ __forceinline__ void acc4(f32x4 v, uint32_t w, int j, float penalty, 
     for (int q = 0; q < 4; ++q) t.sum += expf(v[q] - c);
 }
 
-// value descending, index ascending: the order of argmax_kernel's reductions
-__device__ __forceinline__ bool wins(float ov, int oi, float v, int i) { return ov > v || (ov == v && oi < i); }
+// the n % 4 tail and rows that are not 16-byte aligned: one logit per step, at most one rescale per logit
+__device__ __forceinline__ void acc1(float v, int i, Run& t) {
+    const float m = t.best;
+    take(v, i, t);                                                // ascending per thread as well: strict > keeps the first maximum
+    rescale(m, t);
+    t.sum += expf(v - ref_point(t.best));
+}
 
 template <bool kSeen>
 __global__ __launch_bounds__(kThreads) void logprob_kernel(const float* __restrict__ X, int ldx, int n, uint32_t* seen, int ld_words, float penalty,
@@ -100,38 +95,17 @@ __global__ __launch_bounds__(kThreads) void logprob_kernel(const float* __restri
     }
     const float* x = X + (size_t)r * ldx;
     uint32_t* sr = kSeen ? seen + (size_t)r * ld_words : nullptr;
-    Run t = {-INFINITY, 0x7fffffff, -INFINITY, 0.f};
-    const int n4 = ((reinterpret_cast<uintptr_t>(x) & 15) == 0) ? (n >> 2) : 0;
-    // kUnroll vectors and their bitmap words are loaded before any of them is used (decode_penalty.hip: the loop with one load per iteration
-    // cost 1.295 x there)
-    int j = threadIdx.x;
-    for (; j + (kUnroll - 1) * kThreads < n4; j += kUnroll * kThreads) {
-        f32x4 v[kUnroll];
-        uint32_t w[kUnroll];
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            v[u] = *reinterpret_cast<const f32x4*>(x + 4 * (j + u * kThreads));
-            w[u] = kSeen ? sr[(j + u * kThreads) >> 3] : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) acc4<kSeen>(v[u], w[u], j + u * kThreads, penalty, t);
-    }
-    for (; j < n4; j += kThreads) acc4<kSeen>(*reinterpret_cast<const f32x4*>(x + 4 * j), kSeen ? sr[j >> 3] : 0u, j, penalty, t);
-    for (int j = n4 * 4 + threadIdx.x; j < n; j += kThreads) {    // ascending per thread as well: strict > keeps the first maximum
-        float v = x[j];
-        if (kSeen && ((sr[j >> 5] >> (j & 31)) & 1u)) v = penalised(v, penalty);
-        const float m = t.best;
-        take(v, j, t);
-        rescale(m, t);
-        t.sum += expf(v - ref_point(t.best));
-    }
+    Run t = vr_walk<VR_UNROLL, kSeen>(
+        x, n, sr, Run{-INFINITY, 0x7fffffff, -INFINITY, 0.f},
+        [=](Run t, int j, f32x4 v, uint32_t b) { acc4(v, b, j, penalty, t); return t; },
+        [=](Run t, int i, float v, bool seen_i) { acc1(seen_i ? penalised(v, penalty) : v, i, t); return t; });
     // wave: the selection first (every lane ends with the wave's best / idx / second), then each lane's sum scaled once to the wave's best
     const float own = t.best;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(t.best, o), o2 = __shfl_xor(t.second, o);
         const int oi = __shfl_xor(t.idx, o);
-        if (wins(ov, oi, t.best, t.idx)) { t.second = fmaxf(t.best, o2); t.best = ov; t.idx = oi; }
+        if (vr_before(ov, oi, t.best, t.idx)) { t.second = fmaxf(t.best, o2); t.best = ov; t.idx = oi; }
         else t.second = fmaxf(t.second, ov);                      // (the loser's second is never above its best)
     }
     t.sum = wave_sum(t.sum * scale_to(own, t.best));
@@ -139,18 +113,18 @@ __global__ __launch_bounds__(kThreads) void logprob_kernel(const float* __restri
     __syncthreads();                                              // every read of the row's bitmap by the loops lies in front of this barrier
     if (threadIdx.x == 0) {
         for (int w = 1; w < kWaves; ++w) {
-            if (wins(bv[w], bi[w], t.best, t.idx)) { t.second = fmaxf(t.best, b2[w]); t.best = bv[w]; t.idx = bi[w]; }
+            if (vr_before(bv[w], bi[w], t.best, t.idx)) { t.second = fmaxf(t.best, b2[w]); t.best = bv[w]; t.idx = bi[w]; }
             else t.second = fmaxf(t.second, bv[w]);
         }
         float s = 0.f;
         for (int w = 0; w < kWaves; ++w) s += bs[w] * scale_to(bv[w], t.best);
         const int k = target ? tgt : (t.best > -INFINITY ? t.idx : 0);
         float yk = x[k];
-        if (kSeen && ((sr[k >> 5] >> (k & 31)) & 1u)) yk = penalised(yk, penalty);
+        if (kSeen && vr_seen(sr, k)) yk = penalised(yk, penalty);
         tok[r] = k;
         logprob[r] = (yk - t.best) - logf(s);                     // all -inf: -inf - (-inf) = NaN; s >= 1 otherwise (the maximum's own term)
         if (margin) margin[r] = yk - (k == t.idx ? t.second : t.best);
-        if (kSeen && mark) sr[k >> 5] |= 1u << (k & 31);          // plain read-modify-write: this workgroup is the row's only writer
+        if (kSeen && mark) vr_mark(sr, k);
     }
 }
 

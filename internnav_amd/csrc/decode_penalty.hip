@@ -4,15 +4,16 @@
 //   argmax_penalty_rows  argmax_rows (rope.hip) over the penalised logits, X untouched; optionally marks the chosen token as seen,
 //                        so a chain of decode steps needs no host work and no extra launch between steps
 // Token t is bit t & 31 of word t >> 5. One workgroup per row in both kernels: the row's bitmap has ONE writer, no global atomics.
+// The penalty, the selection order and the walk over a row are those of vocab_row.h, shared with the other token-pick kernels.
 #include <math.h>
 
 #include "common.h"
 #include "kernels.h"
+#include "vocab_row.h"
 
 namespace {
 
-constexpr int kThreads = 1024;
-constexpr int kUnroll = 4;           // 16-byte logit loads in flight per thread in argmax_penalty_rows
+constexpr int kThreads = VR_THREADS;
 constexpr int kSeenMaxWords = 8192;   // LDS bitmap of token_seen_set: 32 KiB = 262144 tokens (Qwen2.5-VL: 152064 tokens = 4752 words, 19 KB)
 
 __global__ __launch_bounds__(kThreads) void token_seen_set_kernel(uint32_t* __restrict__ seen, int ld_words, const int32_t* __restrict__ ids,
@@ -39,67 +40,35 @@ __global__ __launch_bounds__(kThreads) void token_seen_set_kernel(uint32_t* __re
     }
 }
 
-__device__ __forceinline__ float penalised(float x, float penalty) { return x < 0.f ? x * penalty : x / penalty; }   // IEEE fp32 division
+struct Pick { float best; int idx; };   // a thread's running first maximum
 
-// one 16-byte vector of logits (index 4j .. 4j + 3) against the running best of a thread; w = the bitmap word that holds its four bits
-__device__ __forceinline__ void select4(f32x4 v, uint32_t w, int j, float penalty, float& best, int& idx) {
-    const uint32_t b = (w >> ((4 * j) & 31)) & 15u;
-    if (b) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if ((b >> q) & 1u) v[q] = penalised(v[q], penalty);
-    }
+// one 16-byte vector of logits (index 4j .. 4j + 3) and its four seen bits against the running best of a thread
+__device__ __forceinline__ Pick select4(Pick t, f32x4 v, uint32_t b, int j, float penalty) {
+    vr_penalise4(v, b, penalty);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-        if (v[q] > best) { best = v[q]; idx = 4 * j + q; }   // ascending index: the first maximum is kept
+        if (v[q] > t.best) { t.best = v[q]; t.idx = 4 * j + q; }   // ascending index: the first maximum is kept
+    return t;
 }
 
-// The selection of argmax_kernel (rope.hip) over y: first maximum, NaN never selected, no entry above -inf gives 0. The four logits of a
-// 16-byte vector share one bitmap word (4j .. 4j+3 lie in word j >> 3). The division runs only in waves that meet a seen token.
+// The selection of argmax_kernel (rope.hip) over y: first maximum, NaN never selected, no entry above -inf gives 0 (vr_first_max); the
+// row is walked as vocab_row.h lays out.
 __global__ __launch_bounds__(kThreads) void argmax_penalty_kernel(const float* __restrict__ X, int ldx, int n, uint32_t* seen, int ld_words,
                                                                   float penalty, int mark, int32_t* __restrict__ out) {
-    __shared__ float bv[16];
-    __shared__ int bi[16];
-    const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* x = X + (size_t)r * ldx;
+    const int r = blockIdx.x;
     uint32_t* sr = seen + (size_t)r * ld_words;
-    float best = -INFINITY;
-    int idx = 0x7fffffff;
-    const int n4 = ((reinterpret_cast<uintptr_t>(x) & 15) == 0) ? (n >> 2) : 0;
-    // kUnroll vectors and their bitmap words are loaded before any of them is used (a loop with one vector and one word per iteration
-    // measured 1.295 x argmax_kernel at 7 rows of 152064 logits; the figures of this form are in profiles/rep_penalty_b7.txt)
-    int j = threadIdx.x;
-    for (; j + (kUnroll - 1) * kThreads < n4; j += kUnroll * kThreads) {
-        f32x4 v[kUnroll];
-        uint32_t w[kUnroll];
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            v[u] = *reinterpret_cast<const f32x4*>(x + 4 * (j + u * kThreads));
-            w[u] = sr[(j + u * kThreads) >> 3];
-        }
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) select4(v[u], w[u], j + u * kThreads, penalty, best, idx);   // ascending index per thread
-    }
-    for (; j < n4; j += kThreads) select4(*reinterpret_cast<const f32x4*>(x + 4 * j), sr[j >> 3], j, penalty, best, idx);
-    for (int j = n4 * 4 + threadIdx.x; j < n; j += kThreads) {
-        float v = x[j];
-        if ((sr[j >> 5] >> (j & 31)) & 1u) v = penalised(v, penalty);
-        if (v > best || (v == best && j < idx)) { best = v; idx = j; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o);
-        const int oi = __shfl_xor(idx, o);
-        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-    }
-    if (lane == 0) { bv[wave] = best; bi[wave] = idx; }
-    __syncthreads();                                              // every read of the row's bitmap lies in front of this barrier
+    const Pick t = vr_walk<VR_UNROLL, true>(
+        X + (size_t)r * ldx, n, sr, Pick{-INFINITY, 0x7fffffff},
+        [=](Pick t, int j, f32x4 v, uint32_t b) { return select4(t, v, b, j, penalty); },
+        [=](Pick t, int i, float v, bool s) {
+            if (s) v = penalised(v, penalty);
+            if (vr_before(v, i, t.best, t.idx)) { t.best = v; t.idx = i; }
+            return t;
+        });
+    const int tok = vr_first_max(t.best, t.idx);                  // every read of the row's bitmap lies in front of its barrier
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w)
-            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-        const int tok = best > -INFINITY ? idx : 0;
         out[r] = tok;
-        if (mark) sr[tok >> 5] |= 1u << (tok & 31);               // plain read-modify-write: this workgroup is the row's only writer
+        if (mark) vr_mark(sr, tok);
     }
 }
 

@@ -2,7 +2,7 @@
 // logprob launch - HF generate(do_sample=True) with its processors in HF's order (repetition penalty, temperature, top-k, top-p), without a
 // [rows, vocab] tensor leaving the device and without a random number generated here: the uniforms come from the host.
 //   sample_rows   per output row r (logits row s = src ? src[r] : r; seen set, u and the outputs are indexed by r):
-//     1. y = x[s], or the repetition-penalised row (penalised() of decode_penalty.hip over the bits of seen[r]); z = y / T, one IEEE fp32
+//     1. y = x[s], or the repetition-penalised row (penalised() of vocab_row.h over the bits of seen[r]); z = y / T, one IEEE fp32
 //        division (bit-equal to torch's scores / temperature). -0 counts as +0. NaN entries are never kept.
 //     2. top-k (top_k > 0): with k = min(top_k, entries that are not NaN) and v_k the k-th largest z, keep z >= v_k; ties at v_k all stay.
 //     3. top-p (top_p < 1) over what top-k kept, with masses p_i = exp(z_i - max z) / sum: a VALUE v is kept iff the mass of the kept
@@ -20,7 +20,7 @@
 // adds (64-bit LDS atomics) and scans of integers do not depend on the order of arrival, so two launches give the same bits.
 //
 // Shape (mirrored by the bound model of tests/sample_ref.py; change both together):
-//   SAMPLE_THREADS = 1024, SAMPLE_MASS_BITS = 44; a row is walked in quads of 4 logits (16-byte loads where the row's base allows)
+//   SAMPLE_THREADS = 1024 (VR_THREADS), SAMPLE_MASS_BITS = 44; a row is walked in quads of 4 logits by vr_walk_wave (vocab_row.h)
 //   Every pass walks the penalised logits y; z = y / T is monotone in y, so selections run on the keys of y, a threshold found there is taken
 //   to z by one division and back to the lowest y that reaches it by a 32-step bisection - the same kept set as a selection on z, and only
 //   the entries whose mass is needed pay for the division and the expf.
@@ -40,19 +40,17 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "vocab_row.h"
 
 namespace {
 
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / INA_WAVE;
-constexpr int kUnroll = 4;                         // 16-byte logit loads (and their bitmap words) in flight per thread
+constexpr int kThreads = VR_THREADS;
+constexpr int kWaves = VR_WAVES;
 constexpr int kBins = 2048;                        // 11-bit digits: two bins per thread in the scan
 constexpr float kMassScale = 17592186044416.f;    // 2^44
 constexpr int kCand = 1024;                        // entries of the candidate list behind a top-k: one per thread
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ float penalised(float x, float penalty) { return x < 0.f ? x * penalty : x / penalty; }   // IEEE fp32 division
 
 // monotone image of a float that is not NaN: a < b  <=>  key(a) < key(b) (callers turn -0 into +0 first)
 __device__ __forceinline__ uint32_t key_of(float z) {
@@ -64,50 +62,17 @@ __device__ __forceinline__ float value_of(uint32_t k) { return __uint_as_float((
 struct Row {
     const float* x;
     const uint32_t* sr;
-    int n, nq;           // entries, quads of four entries
-    bool vec;            // the row's base is 16-byte aligned
+    int n;
     float penalty, T;
 };
 
-struct Quad {
-    float v[4];
-    uint32_t w;          // the bitmap word of the four logits
-};
-
-// the four logits 4j .. 4j + 3 as they lie in memory, and their bitmap word; an index at or beyond n gives NaN (= not there) and no access
-template <bool kSeen>
-__device__ __forceinline__ Quad load_raw(const Row& R, int j) {
-    Quad Q;
-    const int i0 = 4 * j;
-    if (R.vec && i0 + 3 < R.n) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(R.x + i0);
-        Q.v[0] = t[0]; Q.v[1] = t[1]; Q.v[2] = t[2]; Q.v[3] = t[3];
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) Q.v[q] = (i0 + q < R.n) ? R.x[i0 + q] : NAN;
-    }
-    Q.w = (kSeen && j < R.nq) ? R.sr[j >> 3] : 0u;              // the four logits of a quad share one word; 4j < n: the word exists
-    return Q;
-}
-
-// y of a loaded quad: the penalised logits (-0 -> +0: one key per value). The selections run on y - z = y / T is monotone in y, so the k-th
+// y of a loaded vector: the penalised logits (-0 -> +0: one key per value). The selections run on y - z = y / T is monotone in y, so the k-th
 // largest z is (the k-th largest y) / T and a threshold in z is a threshold in y (`lowest_key_reaching`) - and only the entries whose mass is
 // needed pay for the division and the expf.
-template <bool kSeen>
-__device__ __forceinline__ void finish(const Row& R, int j, const Quad& Q, float (&z)[4]) {
+__device__ __forceinline__ void finish(f32x4 v, uint32_t b, float penalty, float (&z)[4]) {
+    vr_penalise4(v, b, penalty);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) z[q] = Q.v[q];
-    if (kSeen) {
-        const uint32_t b = (Q.w >> ((4 * j) & 31)) & 15u;
-        if (b) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if ((b >> q) & 1u) z[q] = penalised(z[q], R.penalty);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        if (z[q] == 0.f) z[q] = 0.f;
+    for (int q = 0; q < 4; ++q) z[q] = v[q] == 0.f ? 0.f : v[q];
 }
 
 // z of a penalised logit: one IEEE fp32 division (-0 -> +0)
@@ -127,34 +92,20 @@ __device__ __forceinline__ uint32_t lowest_key_reaching(float v, uint32_t lo, ui
     return lo;
 }
 
-// One pass over the row: f(j, y) for every quad j. Thread t takes quads t, t + 1024, ...: the 64 quads of a CHUNK (256 token ids) lie in
-// one wave, and a wave runs f on whole chunks (lanes beyond the row see NaN), so f may use wave shuffles. kUnroll quads and their bitmap
-// words are loaded before any of them is used (decode_penalty.hip: one load per iteration left the loop latency-bound).
-template <bool kSeen, typename F>
-__device__ __forceinline__ void for_quads(const Row& R, F f) {
-    const int n4 = R.vec ? (R.n >> 2) : 0;                        // whole quads of an aligned row: 16-byte loads without a branch
-    int j = threadIdx.x;
-    for (; (j | 63) + (kUnroll - 1) * kThreads < n4; j += kUnroll * kThreads) {      // (the wave's last lane decides: uniform over the wave)
-        Quad Q[kUnroll];
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(R.x + 4 * (j + u * kThreads));
-            Q[u].v[0] = t[0]; Q[u].v[1] = t[1]; Q[u].v[2] = t[2]; Q[u].v[3] = t[3];
-            Q[u].w = kSeen ? R.sr[(j + u * kThreads) >> 3] : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            float z[4];
-            finish<kSeen>(R, j + u * kThreads, Q[u], z);
-            f(j + u * kThreads, z);
-        }
-    }
-    for (; (j & ~63) < R.nq; j += kThreads) {                     // rows that are not aligned, the last rounds, the n % 4 tail
+// One pass over the row: st = f(st, j, y) for every quad j, in the whole-wave form of the walk (vocab_row.h): a wave runs f on whole chunks
+// of 64 quads (256 token ids; lanes beyond the row see NaN), so f may use wave shuffles. The thread's running state goes through f by value.
+template <bool kSeen, typename St, typename F>
+__device__ __forceinline__ St for_quads(const Row& R, St st, F f) {
+    const float penalty = R.penalty;
+    return vr_walk_wave<VR_UNROLL, kSeen>(R.x, R.n, R.sr, st, [=](St st, int j, f32x4 v, uint32_t b) {
         float z[4];
-        finish<kSeen>(R, j, load_raw<kSeen>(R, j), z);
-        f(j, z);
-    }
+        finish(v, b, penalty, z);
+        return f(st, j, z);
+    });
 }
+
+struct NoState {};      // the state of a pass that keeps nothing per thread
+struct Span { float mx, mn; uint32_t cnt; };   // pass 0
 
 __device__ __forceinline__ u64 mass_of(float y, float T, float M) {
     const float z = z_of(y, T);
@@ -220,7 +171,7 @@ __device__ uint32_t radix_select(const Row& R, float M, uint32_t floor_key, u64 
         S.hist[2 * threadIdx.x + 1] = 0;
         if (threadIdx.x == 0) { S.sel_bin = 0; S.sel_above = above; }
         __syncthreads();
-        for_quads<kSeen>(R, [&](int j, const float (&z)[4]) {
+        for_quads<kSeen>(R, NoState{}, [&](NoState st, int j, const float (&z)[4]) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 if (z[q] != z[q]) continue;
@@ -233,6 +184,7 @@ __device__ uint32_t radix_select(const Row& R, float M, uint32_t floor_key, u64 
                 const u64 h = kMass ? mass_of(z[q], R.T, M) : 1ull;
                 if (h) atomicAdd(&S.hist[(k >> shift) & ((1u << bits) - 1u)], h);
             }
+            return st;
         });
         __syncthreads();
         const u64 h0 = S.hist[2 * threadIdx.x], h1 = S.hist[2 * threadIdx.x + 1];
@@ -275,19 +227,18 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* __restric
     R.x = X + (size_t)s * ldx;
     R.sr = sr;
     R.n = n;
-    R.nq = (n + 3) >> 2;
-    R.vec = (reinterpret_cast<uintptr_t>(R.x) & 15) == 0;
     R.penalty = penalty;
     R.T = T;
 
     // ---- pass 0: maximum, minimum, number of entries that are not NaN
-    float mx = -INFINITY, mn = INFINITY;
-    uint32_t cnt = 0;
-    for_quads<kSeen>(R, [&](int, const float (&z)[4]) {
+    const Span sp = for_quads<kSeen>(R, Span{-INFINITY, INFINITY, 0u}, [](Span t, int, const float (&z)[4]) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            if (z[q] == z[q]) { mx = fmaxf(mx, z[q]); mn = fminf(mn, z[q]); ++cnt; }
+            if (z[q] == z[q]) { t.mx = fmaxf(t.mx, z[q]); t.mn = fminf(t.mn, z[q]); ++t.cnt; }
+        return t;
     });
+    float mx = sp.mx, mn = sp.mn;
+    uint32_t cnt = sp.cnt;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         mx = fmaxf(mx, __shfl_xor(mx, o));
@@ -364,7 +315,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* __restric
                 const float Wf = (float)((double)W * (1.0 / 17592186044416.0));
                 const float zt = z_of(yt, T);
                 logprob[r] = (zt == M ? 0.f : zt - M) - logf(Wf);
-                if (kSeen && mark) sr[it >> 5] |= 1u << (it & 31);     // the row's only writer, behind every read of the bitmap
+                if (kSeen && mark) vr_mark(sr, it);                // behind every read of the bitmap
             }
             return;
         }
@@ -379,14 +330,14 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* __restric
     S.hist[threadIdx.x] = 0;                                      // (chunks beyond the row)
     if (threadIdx.x == 0) { S.sel_bin = 0; S.sel_above = 0; }
     __syncthreads();
-    cnt = 0;
-    for_quads<kSeen>(R, [&](int j, const float (&z)[4]) {
+    cnt = for_quads<kSeen>(R, 0u, [&](uint32_t c, int j, const float (&z)[4]) {
         u64 m = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            if (z[q] == z[q] && key_of(z[q]) >= floor_key) { m += mass_of(z[q], T, M); ++cnt; }
+            if (z[q] == z[q] && key_of(z[q]) >= floor_key) { m += mass_of(z[q], T, M); ++c; }
         m = wave_sum_u64(m);
         if (lane == 0) S.hist[j >> 6] = m;
+        return c;
     });
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
@@ -416,8 +367,11 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* __restric
     // ---- draw, pass B: one wave walks the chunk that holds the target with a 64-lane integer scan
     const int j = (int)S.sel_bin * 64 + lane;
     const u64 run = S.sel_above;
+    f32x4 vq;
+    uint32_t bq;
+    vr_load_padded<kSeen>(R.x, n, sr, j, vq, bq);
     float z[4];
-    finish<kSeen>(R, j, load_raw<kSeen>(R, j), z);
+    finish(vq, bq, penalty, z);
     u64 mq[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) mq[q] = (z[q] == z[q] && key_of(z[q]) >= floor_key) ? mass_of(z[q], T, M) : 0;
@@ -445,7 +399,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* __restric
         const float Wf = (float)((double)W * (1.0 / 17592186044416.0));
         const float zt = z_of(yq, T);
         logprob[r] = (zt == M ? 0.f : zt - M) - logf(Wf);
-        if (kSeen && mark) sr[t >> 5] |= 1u << (t & 31);          // plain read-modify-write: this workgroup is the row's only writer
+        if (kSeen && mark) vr_mark(sr, t);
     }
 }
 

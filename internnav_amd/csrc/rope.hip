@@ -5,6 +5,7 @@
 //   argmax_rows   greedy token selection over the vocabulary
 #include "common.h"
 #include "kernels.h"
+#include "vocab_row.h"
 
 namespace {
 
@@ -90,40 +91,28 @@ __global__ __launch_bounds__(256) void mrope_table_kernel(MropeTableArgs p) {
     }
 }
 
-// 1024 threads per row, 16-byte loads: the row (152064 logits = 594 KiB) is a single latency-bound stream for one workgroup.
+// 1024 threads per row, 16-byte loads: the row (152064 logits = 594 KiB) is a single latency-bound stream for one workgroup. The walk over
+// the row, the selection order and the block reduction are those of vocab_row.h, here without a seen set and with one vector per iteration.
 // NaN entries never compare greater and are never selected; a row without any entry above -inf (all -inf, all NaN) gives 0, as torch.argmax
 // does for all -inf: the result indexes the embedding table of the next launch and is always in [0, n).
-__global__ __launch_bounds__(1024) void argmax_kernel(ArgmaxArgs p) {
-    __shared__ float bv[16];
-    __shared__ int bi[16];
-    const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* x = p.X + (size_t)r * p.ldx;
-    float best = -INFINITY;
-    int idx = 0x7fffffff;
-    const int n4 = ((reinterpret_cast<uintptr_t>(x) & 15) == 0) ? (p.n >> 2) : 0;
-    for (int j = threadIdx.x; j < n4; j += 1024) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * j);
+struct Pick { float best; int idx; };   // a thread's running first maximum
+
+__global__ __launch_bounds__(VR_THREADS) void argmax_kernel(ArgmaxArgs p) {
+    const int r = blockIdx.x;
+    const Pick t = vr_walk<1, false>(
+        p.X + (size_t)r * p.ldx, p.n, nullptr, Pick{-INFINITY, 0x7fffffff},
+        [](Pick t, int j, f32x4 v, uint32_t) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (v[q] > best) { best = v[q]; idx = 4 * j + q; }   // ascending index per thread: the first maximum is kept
-    }
-    for (int j = n4 * 4 + threadIdx.x; j < p.n; j += 1024) {
-        const float v = x[j];
-        if (v > best || (v == best && j < idx)) { best = v; idx = j; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o);
-        const int oi = __shfl_xor(idx, o);
-        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-    }
-    if (lane == 0) { bv[wave] = best; bi[wave] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w)
-            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-        p.out[r] = best > -INFINITY ? idx : 0;   // no entry above -inf: idx is the start value or whichever -inf a scalar tail met
-    }
+            for (int q = 0; q < 4; ++q)
+                if (v[q] > t.best) { t.best = v[q]; t.idx = 4 * j + q; }   // ascending index per thread: the first maximum is kept
+            return t;
+        },
+        [](Pick t, int i, float v, bool) {
+            if (vr_before(v, i, t.best, t.idx)) { t.best = v; t.idx = i; }
+            return t;
+        });
+    const int tok = vr_first_max(t.best, t.idx);
+    if (threadIdx.x == 0) p.out[r] = tok;
 }
 
 }  // namespace

@@ -150,7 +150,8 @@ class Selection:
     def _pick(self, B: int, R: int, col: int, src: Optional[torch.Tensor]):
         """the chosen token of R output rows from B logits rows (src int32 [R]: the logits row of each output row; None = its own) ->
         next_tok[:R]. With a repetition penalty the pick runs over the penalised logits of the tokens in `seen` and marks the chosen one
-        (`logits` keeps the unpenalised values).
+        (`logits` keeps the unpenalised values). The four paths are interchangeable because their kernels share one penalised value, one
+        selection order and one walk over a row: csrc/vocab_row.h.
           beam search     ops.beam_topm_rows (log-softmax, the penalty on the log-probabilities over the CURRENT seen set, + running score,
                           the M best per row) followed by ops.beam_step (the prompts' bookkeeping)
           sampling        ops.sample_rows - temperature, top-k, top-p and the draw against row `col` of the state's uniform table; the

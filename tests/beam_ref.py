@@ -20,7 +20,7 @@ Rules (per prompt; K = num_beams, M = max(2, 1 + n_eos) * K, step j produces ans
   (finished_k ? min(all K finished scores) : -1e9)). Done: flag off, or early_stopping is True and all K finished, or all M candidates hit.
   A done prompt is frozen.
 
-Summation shape of beam_topm_rows (change both together):
+Summation shape of beam_topm_rows (the walk is vr_walk of csrc/vocab_row.h; change both together):
   BEAM_THREADS = 1024; the row maximum is exact; sum exp(x - max): aligned rows in 16-byte vectors - thread t takes vectors t, t + 1024, ... and
   adds their terms in ascending index; rows whose base is not 16-byte aligned, and the n % 4 tail, one logit per step. A wave's 64 sums are
   added in a 6-level butterfly, the 16 wave sums sequentially. expf / logf of the device library (2 ulp).

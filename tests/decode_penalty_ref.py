@@ -1,5 +1,6 @@
 """fp32 restatement on the CPU of the repetition penalty of greedy decoding (transformers RepetitionPenaltyLogitsProcessor under
-generate(do_sample=False)) and of the engine's selection rule: what csrc/decode_penalty.hip is tested against, bit for bit.
+generate(do_sample=False)) and of the engine's selection rule: what csrc/decode_penalty.hip is tested against, bit for bit
+(penalised(), the bitmap layout and the selection order are defined once for all token-pick kernels, in csrc/vocab_row.h).
 
     seen_bitmap(ids, lens, n)          uint32 [rows, ceil(n / 32)]: token t of row r is bit t & 31 of word t >> 5
     penalised(x, bitmap, p)            fp32: x where the bit is clear, else x * p for x < 0 and x / p otherwise (numpy's fp32 division is

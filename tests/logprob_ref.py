@@ -10,7 +10,8 @@ Restatement, per row (x fp32 [n], bitmap = the row's seen set or None, p the pen
 
 Bound on |logprob_kernel - logprob_float64| (derived from the number formats and the kernel's summation shape; nothing in it comes from a kernel's
 output). u = 2^-24 is the rounding of one fp32 operation, ulp = 2^-23; expf and logf are taken as 2-ulp functions (the device library documents
-1 ulp for both). The constants below mirror the header comment of decode_logprob.hip.
+1 ulp for both). The constants below mirror the header comment of decode_logprob.hip; the per-thread order of the walk (LOGPROB_THREADS,
+LOGPROB_VEC) is that of vr_walk in csrc/vocab_row.h.
   * one term exp(y - c): 2 ulp of expf + the rounding of its argument, |fl(y - c) - (y - c)| <= u |y - c|, i.e. a relative u * D with
     D = max |y - max y|. A term with y - c < -104 is 0 in fp32 and below 2^-149 exactly, so D is capped at 104 and n * 2^-149 is added;
   * a thread adds T terms sequentially (T u) and rescales its sum at most R times, once per 16-byte vector (or per logit on the one-by-one

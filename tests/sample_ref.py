@@ -18,8 +18,8 @@ Acceptance (no row is ever excluded). The kernel reports its threshold, so the c
     m64 <= 1 - top_p + eps; with top_p == 1 iff it EQUALS v_k (the smallest entry when top-k is off);
   * a token j passes iff z_j >= thr (not NaN) and c[j-1] - eps <= u < c[j] + eps on the float64 inclusive CDF c of the set {z >= thr}.
 
-eps, in CDF units, from the kernel's summation shape (header of decode_sample.hip; nothing in it comes from a kernel's output). U = 2^-24 is the
-rounding of one fp32 operation, ULP = 2^-23, expf / logf are taken as 2-ulp functions as in logprob_ref.py. An entry's mass is
+eps, in CDF units, from the kernel's summation shape (header of decode_sample.hip, the walk of csrc/vocab_row.h; nothing in it comes from a
+kernel's output). U = 2^-24 is the rounding of one fp32 operation, ULP = 2^-23, expf / logf are taken as 2-ulp functions as in logprob_ref.py. An entry's mass is
 trunc(expf(fl(z - M)) * 2^44) as an integer and EVERY sum is an exact integer sum, so a sum adds no rounding at all:
   * a mass that does not vanish has z - M >= -44 ln 2, so the rounding of its argument is a relative U * D of the term with
     D = min(max |z - M|, 44 ln 2 + 1), next to the 2 ULP of expf: rel = 2 ULP + U * D per term, hence of any sum of terms;

@@ -129,7 +129,7 @@ def _check_rows(ops, x, run, M, src, seen_bits, penalty, ldx=None, ref=None):
     return worst
 
 
-@pytest.mark.parametrize("n", [97, 4096, 4099, 152064])
+@pytest.mark.parametrize("n", [97, 4096, 4099, 12288, 12400, 12547, 16384, 16389, 28675, 152064])
 @pytest.mark.parametrize("rows", [1, 3, 28])
 @pytest.mark.parametrize("M", [2, 6, 24, 32])
 @pytest.mark.parametrize("with_src", [False, True])

@@ -16,7 +16,7 @@ from internnav_amd import synthetic as S
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 PATTERN = 0xA5A5A5A5
-NS = [1, 31, 32, 33, 127, 4096, 4099, 152064]
+NS = [1, 31, 32, 33, 127, 4096, 4099, 12288, 12400, 12547, 16384, 16389, 28675, 152064]
 
 
 @pytest.fixture(scope="module")

@@ -16,7 +16,7 @@ import logprob_ref as L
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 PATTERN = 0xA5A5A5A5
-NS = [1, 3, 4, 5, 31, 32, 33, 4097, 152064]
+NS = [1, 3, 4, 5, 31, 32, 33, 4097, 12288, 12400, 12547, 16384, 16389, 28675, 152064]
 SENT_I, SENT_F = -7, 123.5
 
 

@@ -290,7 +290,7 @@ def test_argmax_rows_tie_placements(ops, aligned):
 
 
 @pytest.mark.parametrize("aligned", [True, False], ids=["aligned", "unaligned"])
-@pytest.mark.parametrize("n", [1, 3, 4, 1023, 1024, 152064, 152065])
+@pytest.mark.parametrize("n", [1, 3, 4, 1023, 1024, 12288, 12400, 12547, 16384, 16389, 28675, 152064, 152065])
 def test_argmax_rows_sizes_and_edges(ops, n, aligned):
     """random rows, rows holding -inf entries, the maximum at either end; then the rows without a maximum: all -inf -> 0 (torch.argmax),
     all NaN -> some index in [0, n); NaN entries next to finite ones are never chosen."""

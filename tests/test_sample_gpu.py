@@ -16,7 +16,7 @@ import sample_ref as S
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 PATTERN = 0xA5A5A5A5
-NS = [1, 3, 4, 5, 31, 32, 33, 4097, 152064]
+NS = [1, 3, 4, 5, 31, 32, 33, 4097, 12288, 12400, 12547, 16384, 16389, 28675, 152064]
 CONFIGS = [(1.0, 0, 1.0), (0.7, 50, 0.9), (1.0, 0, 0.9), (1.3, 1, 1.0), (1e-6, 0, 0.001)]      # (T, top_k, top_p)
 SENT_I, SENT_F = -7, 123.5
 
